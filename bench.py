@@ -15,16 +15,24 @@ K timed env-steps of the RolloutPhase hot loop: render + ACT every `skip` = 3 st
 ensemble, command routing, 8 physics substeps, observation, success predicate and phase
 bookkeeping, all on the device.  One `step` = one env-step of every env.  The ACT decoder runs
 layer 0 only: the DETRVAE output reads that layer's normed intermediate, layers 1..6 are dead
-(exact; tests/test_act_full_gpu.py; --act_full_decoder runs all seven); the JSON line also prices
-the step with all seven computed (`all_decoder_layers`, from one isolated 7-layer call).
+(exact; tests/test_act_full_gpu.py; --act_full_decoder runs all seven).
 
-The same workload with the policy in bf16 (throughput mode) is reported as `secondary_bf16`
-with its measured action error against fp32 on the same inputs; it is never `value`.
+A plain run does only what the headline needs: set-up, the W warm-up and K timed env-steps, and
+ONE JSON line (rank 0) with `value` (env-steps/s), `ms_per_step` (wall milliseconds per timed
+env-step) and the per-phase split of the timed steps.  `--dump-outputs DIR` also writes what the
+last timed env-step left in the caller's hands (observation, reward, policy action, commands,
+physics state, episode records and a fixed sample of the policy's camera frames) as
+DIR/<name>.npy; the inputs are seeded, so two builds can be compared array for array.
 
-Prints ONE JSON line (rank 0) with the roofline of the physics kernels (algorithmic bytes per
-env-step / HIP-event kernel time), FP64 and policy-MFMA fractions, and the CPU
-baseline (the oracle's C physics + ACT in PyTorch-CPU: a throughput leg of single-threaded
-1-env processes, a 1-env latency leg and the C1 MLP leg, on bounded samples).
+`--full` adds everything else to the line, each from runs of its own after the timed steps: the
+isolated physics / policy probes and the roofline of the physics kernels (algorithmic bytes per
+env-step / HIP-event kernel time), FP64 and policy-MFMA fractions; the step priced
+with all seven decoder layers computed (`all_decoder_layers`, from one isolated 7-layer call);
+the 512-env configs[2] per-rank workload (`c3_per_rank`); the same workload with the policy in
+bf16 (throughput mode, `secondary_bf16`, with its measured action error against fp32 on the same
+inputs; it is never `value`); and the CPU baseline (the oracle's C physics + ACT in PyTorch-CPU:
+a throughput leg of single-threaded 1-env processes, a 1-env latency leg and the C1 MLP leg, on
+bounded samples).  The --no_* switches drop single legs of a --full run.
 """
 
 import argparse
@@ -336,6 +344,11 @@ def parse(argv=None):
     p.add_argument("--groups", type=int, default=1,
                    help="env groups per GPU, each on its own HIP stream with its policy steps offset by one env-step "
                         "(measured: no gain at 1024 envs, DESIGN.md section 5)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the isolated probes / rooflines, the 512-env per-rank line, the bf16 secondary "
+                        "and the CPU baseline (each a run of its own after the timed steps)")
+    p.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                   help="write the arrays the last timed env-step produced as DIR/<name>.npy (rank 0)")
     p.add_argument("--no_bf16_secondary", action="store_true")
     p.add_argument("--no_cpu_baseline", action="store_true")
     p.add_argument("--no_c3_per_rank", action="store_true", help="skip the 512-env configs[2] per-rank line")
@@ -513,9 +526,52 @@ def make_rollout(args, dev, precision, n_local, g0):
     return ro
 
 
-def timed_run(groups, args, dist):
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: all files together
+DUMP_FRAME_ENVS = 4  # envs whose policy camera frame is dumped (seeded choice)
+
+
+def dump_outputs(groups, out_dir):
+    """Write what the last env-step of `groups` handed its caller as out_dir/<name>.npy (float64
+    where the device array is f64, else float32), the groups' envs concatenated in env order:
+    the observation, reward, the ensembled policy action, the routed commands, the physics state
+    (qpos, qvel, time), the per-env episode records and the policy tensor of the camera frames
+    (as the renderer wrote it at the last inference) of DUMP_FRAME_ENVS envs of group 0 chosen by
+    a seeded generator.  Returns {name: shape}."""
+    from robomanipbaselines_amd import kernels as K
+
+    def host(t):
+        t = t.detach()
+        return t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+
+    per_group = []
+    for ro in groups:
+        eng = ro.env.engine
+        d = {f"obs_{k}": host(v) for k, v in sorted(ro.obs.items())}
+        d.update(reward=host(ro.reward), policy_action=host(ro.policy_action), command_joint_pos=host(ro.q_cmd),
+                 command_gripper=host(ro.grip_cmd), qpos=host(eng.qpos), qvel=host(eng.qvel), time=host(eng.time))
+        v = K.sched_view(ro.sched)
+        for k in ("success", "result_reward", "duration", "rollout_time_idx"):
+            d[f"episode_{k}"] = np.ascontiguousarray(v[k]).astype(np.float64)
+        per_group.append(d)
+    out = {k: np.concatenate([d[k] for d in per_group]) for k in per_group[0]}
+    img = getattr(groups[0], "_img", None)
+    if img is not None:
+        idx = np.sort(np.random.default_rng(0).choice(groups[0].n, min(DUMP_FRAME_ENVS, groups[0].n), replace=False))
+        out["policy_frame_envs"] = idx.astype(np.float64)
+        out["policy_frame"] = host(img[torch.from_numpy(idx).to(img.device)])
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte cap")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {k: list(a.shape) for k, a in out.items()}
+
+
+def timed_run(groups, args, dist, probes=True, dump_dir=None):
     """W warm-up + K timed env-steps of every group, group g on HIP stream g (its policy steps
-    offset by g env-steps: group g takes g extra warm-up steps), then isolated probes: the physics
+    offset by g env-steps: group g takes g extra warm-up steps); `dump_dir`: dump_outputs of the
+    state the last timed step left.  With `probes`, then isolated probes: the physics
     launch sequence of every group and one infer_policy call of group 0, each bracketed by HIP
     events with nothing else queued (in-loop events would include the other groups' kernels)."""
     streams = [torch.cuda.current_stream()] + [torch.cuda.Stream() for _ in groups[1:]]
@@ -572,9 +628,11 @@ def timed_run(groups, args, dist):
         torch.cuda._sleep(1000)
         torch.cuda.synchronize()
     progress(f"timed {args.steps} steps: {elapsed:.3f} s")
+    if dump_dir is not None:
+        progress(f"outputs written to {dump_dir}: {dump_outputs(groups, dump_dir)}")
     # isolated probes (after the timed region)
     phys = []
-    for _ in range(3):
+    for _ in range(3 if probes else 0):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for ro in groups:
@@ -583,7 +641,7 @@ def timed_run(groups, args, dist):
         torch.cuda.synchronize()
         phys.append(e0.elapsed_time(e1))
     infer = []
-    for _ in range(2):
+    for _ in range(2 if probes else 0):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         groups[0].infer_policy()
@@ -593,7 +651,7 @@ def timed_run(groups, args, dist):
     # the same call with all 7 decoder layers computed (the dead layers 1..6 included), for the
     # sensitivity line `all_decoder_layers`: the second call is timed
     infer_full = []
-    pol = getattr(groups[0], "policy", None)
+    pol = getattr(groups[0], "policy", None) if probes else None
     if pol is not None and getattr(pol, "prune_dead_decoder", False):
         pol.prune_dead_decoder = False
         for _ in range(2):
@@ -668,7 +726,8 @@ def rank_main(args):
 
     groups = make_groups(args.precision)
     ro = groups[0]
-    elapsed, phys, infer, infer_full, phases = timed_run(groups, args, dist)
+    elapsed, phys, infer, infer_full, phases = timed_run(groups, args, dist, probes=args.full,
+                                                         dump_dir=args.dump_outputs if rank == 0 else None)
     value = total * args.steps / elapsed
     if dist:
         # RCCL all-gather of per-env episode records (success, reward, duration, steps)
@@ -678,16 +737,6 @@ def rank_main(args):
             parts.append(pack_results(v["success"], v["result_reward"], v["duration"], v["rollout_time_idx"]))
         gathered = gather_results(np.concatenate(parts), dev)
         assert gathered.shape[0] == total
-    eng = ro.env.engine
-    st = np.concatenate([r.env.engine.stats.cpu().numpy() for r in groups])
-    bytes_env_step = algorithmic_bytes_per_env_step(eng.nq, eng.nv, eng.nu, 8)
-    kern_s = float(phys.mean()) / 1e3
-    achieved = n * bytes_env_step / kern_s / 1e9
-    ncon, nefc, iters = float(st[:, 0].mean()), float(st[:, 1].mean()), float(st[:, 2].mean())
-    fl_sub = physics_flops_per_substep(ncon, nefc, iters)
-    fp64_tf = n * 8 * fl_sub / kern_s / 1e12
-    traffic_env, traffic_src = pmc_traffic_per_env_step()
-    pol_flops = policy_flops_per_inference(args.act_full_decoder)
     result = {
         "metric": "env-steps/s (whole node) + policy-inference us/step, MujocoUR5eCable x N ACT",
         "value": round(value, 1),
@@ -708,6 +757,26 @@ def rank_main(args):
                                    else "single GPU (no collective)"),
                    "env_groups": G,
                    "act_decoder_layers_run": 7 if args.act_full_decoder else 1},
+    }
+    if phases is not None:
+        result["phases"] = phases
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if dist:
+            tdist.destroy_process_group()
+        return
+    eng = ro.env.engine
+    st = np.concatenate([r.env.engine.stats.cpu().numpy() for r in groups])
+    bytes_env_step = algorithmic_bytes_per_env_step(eng.nq, eng.nv, eng.nu, 8)
+    kern_s = float(phys.mean()) / 1e3
+    achieved = n * bytes_env_step / kern_s / 1e9
+    ncon, nefc, iters = float(st[:, 0].mean()), float(st[:, 1].mean()), float(st[:, 2].mean())
+    fl_sub = physics_flops_per_substep(ncon, nefc, iters)
+    fp64_tf = n * 8 * fl_sub / kern_s / 1e12
+    traffic_env, traffic_src = pmc_traffic_per_env_step()
+    pol_flops = policy_flops_per_inference(args.act_full_decoder)
+    result.update({
         "policy_inference_us_per_call": round(1e6 * float(infer.mean()), 1) if len(infer) else None,
         "policy_inference_batch": groups[0].n,
         "policy_inference_us_per_env_step": round(1e6 * float(infer.mean()) / (groups[0].n * ro.args.skip), 3) if len(infer) else None,
@@ -726,9 +795,7 @@ def rank_main(args):
                           "kernel": "physics env-step: 8 x (rmbx::front_kernel + rmbx::solver_kernel)",
                           "algorithmic_flops_per_substep": round(fl_sub)},
         "contacts_mean": ncon, "constraint_rows_mean": nefc, "newton_iters_mean": iters,
-    }
-    if phases is not None:
-        result["phases"] = phases
+    })
     if len(infer):
         pol_tf = groups[0].n * pol_flops / float(infer.mean()) / 1e12
         peak = MFMA_PEAK_TFLOPS[args.precision]
