@@ -300,7 +300,8 @@ int rmbx_motion_command(const double* placement, const double* action, int actio
  * = (geom id, type, -, -), prim_f32 [nprim][8] = (size3, rgb3, -, -).  Geom frames come from the
  * engine outputs gxpos/gxmat; the camera frame from body xpos/xquat + camera offset.
  * Outputs (each optional): rgb u8 [n][H][W][3]; depth f32 [n][H][W] (linear camera-z distance,
- * the quantity MujocoEnvBase.py:122-125 recovers); policy tensor [n][3][H][W] in bf16 (dtype 1)
+ * the quantity MujocoEnvBase.py:122-125 recovers; a background pixel, where no surface is hit,
+ * holds cam->zfar exactly); policy tensor [n][3][H][W] in bf16 (dtype 1)
  * or f32 (dtype 0) = ((u8 / 255) - mean[c]) / std[c] (RolloutBase.py:479-490 + ImageNet
  * normalisation of the ACT/MLP backbones), or (dtype 2) the same values in bf16 as a 2x2
  * space-to-depth image [n][H/2][W/2][16] (channel (dy*2+dx)*3+c, 12..15 zero) for
@@ -363,10 +364,12 @@ typedef struct rmbx_scene_tables {
    * density in base texels per metre -- 2d: max(rx W, ry H) per metre of repeat, cube: max(W, H) /
    * (2 |major axis coordinate|); bilinear per level, texel centres at +0.5): 2d from the hit's
    * local (x, y), repeated
-   * texrepeat times over the geom's (2 size_x, 2 size_y) extent, or per metre when texuniform or
+   * texrepeat times over the geom's (2 size_x, 2 size_y) extent (a sphere, capsule or cylinder:
+   * its diameter 2 size_0 in both), or per metre when texuniform or
    * the plane is infinite; cube from the local hit point (divided by the geom's half extents when
-   * texuniform) as a cube-map direction, the same image on all six faces, OpenGL's face
-   * orientation, clamped at the face edges.  Shading: material colour x texture x (0.1 ambient +
+   * texuniform: box size, sphere (r, r, r), capsule (r, r, r + half length), cylinder (r, r, half
+   * length), plane (size_x, size_y, 1), a zero extent left undivided) as a cube-map direction,
+   * the same image on all six faces, OpenGL's face orientation, clamped at the face edges.  Shading: material colour x texture x (0.1 ambient +
    * 0.6 headlight |n.v| + 0.3 max(0, n.z) + emission) + specular x 0.3 x max(0, n.h)^(128
    * shininess) for the directional light (world +z towards it, h the half vector), clamped at 1. */
   const int32_t* geom_texid;

@@ -7,44 +7,9 @@ formula, on a synthetic scene (no GPU)."""
 import numpy as np
 
 from oracle import render as OR
+from render_cases import scene as _scene
 
 W, H = 64, 48
-
-
-def _scene(objects, cam_pos=(0.0, 0.0, 0.0), cam_quat=(1.0, 0.0, 0.0, 0.0), fovy=45.0, tris=None):
-    """Minimal compiled-scene arrays: objects = [(type, size3, pos3, rgb3)], a world-body camera
-    looking along -z; tris: [m, 3, 3] triangles of one mesh geom at the origin (type 7)."""
-    n = len(objects) + (1 if tris is not None else 0)
-    a = {"geom_type": np.zeros(n, np.int32), "geom_group": np.zeros(n, np.int32),
-         "geom_ctype": np.full(n, -1, np.int32), "geom_csize": np.zeros((n, 3)), "geom_size": np.zeros((n, 3)),
-         "geom_rgba": np.ones((n, 4)), "names_cam": np.array(["cam"]), "cam_body": np.array([0], np.int32),
-         "cam_pos": np.array([cam_pos], np.float64), "cam_quat": np.array([cam_quat], np.float64),
-         "cam_fovy": np.array([fovy]), "_znear": np.float64(0.01), "_extent": np.float64(2.0)}
-    pos = np.zeros((n, 3))
-    for g, (t, size, p, rgb) in enumerate(objects):
-        a["geom_type"][g] = t
-        a["geom_size"][g] = size
-        a["geom_rgba"][g, :3] = rgb
-        pos[g] = p
-    if tris is not None:  # one mesh geom on the world body, its triangles in the body frame
-        g = n - 1
-        a["geom_type"][g] = 7
-        a["geom_rgba"][g, :3] = (0.5, 0.5, 0.5)
-        t = np.asarray(tris, np.float64)
-        e1, e2 = t[:, 1] - t[:, 0], t[:, 2] - t[:, 0]
-        nrm = np.cross(e1, e2)
-        nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
-        packed = np.zeros((len(t), 16), np.float32)
-        packed[:, 0:3], packed[:, 3:6], packed[:, 6:9], packed[:, 9:12] = t[:, 0], e1, e2, nrm
-        packed[:, 12] = np.full(len(t), g, np.int32).view(np.float32)
-        packed[:, 13:16] = (0.5, 0.5, 0.5)
-        a["rmesh_body"] = np.array([0], np.int32)
-        a["rmesh_geoms"] = np.array([g], np.int32)
-        a["rmesh_tri_adr"] = np.array([0], np.int32)
-        a["rmesh_tri_num"] = np.array([len(t)], np.int32)
-        a["rmesh_tri"] = packed
-    gxmat = np.tile(np.eye(3).reshape(1, 9), (n, 1))
-    return a, pos, gxmat
 
 
 def _cast(a, pos, gxmat, pix):
