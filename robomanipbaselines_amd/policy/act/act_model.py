@@ -20,6 +20,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..backbone import FusedResNet18Trunk, ResNet18Trunk
+from ..derived import derived
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -62,29 +63,24 @@ def _x6_ok(x, n_out):
     return K.linear_f32x6_supported(x, n_out)
 
 
-def _x6_planes(owner, name, w):
-    """pack_f32_weight(w) (the f16x3 or bf16x6 pieces), cached on `owner` per weight storage and version."""
+def _x6_planes(owner, name, w, sources=None):
+    """pack_f32_weight(w) (the f16x3 or bf16x6 pieces), held on `owner` (derived: rebuilt when w, or
+    the parameters `sources` that w was computed from, change)."""
     from ... import kernels as K
 
-    key = (w.data_ptr(), w._version, tuple(w.shape))
-    cache = owner.__dict__.setdefault("_x6", {})
-    ent = cache.get(name)
-    if ent is None or ent[0] != key:
-        ent = (key, K.pack_f32_weight(w.detach().contiguous()))
-        cache[name] = ent
-    return ent[1]
+    return derived(owner, name, (w,) if sources is None else sources, lambda: K.pack_f32_weight(w.detach().contiguous()))
 
 
-def _x6_linear(owner, name, x, w, b, relu=False):
+def _x6_linear(owner, name, x, w, b, relu=False, sources=None):
     from ... import kernels as K
 
-    return K.linear_f32x6(x, _x6_planes(owner, name, w), b, relu=relu)
+    return K.linear_f32x6(x, _x6_planes(owner, name, w, sources), b, relu=relu)
 
 
 def _x6_linear_padded(owner, name, x, w, b):
     """F.linear(x, w, b) on rmbx_linear_f32x6 for shapes it does not take directly (N not a multiple
     of 128, K not a multiple of 32: the proprio projection 7 -> 512, the action head 512 -> 7): W and
-    b zero-padded once (cached per weight storage and version), x zero-padded along K when needed,
+    b zero-padded once (derived from w and b), x zero-padded along K when needed,
     the first N columns returned.  fp32-accurate like the other device GEMMs, and every row's
     result is independent of the batch size (hipBLASLt chooses its algorithm by the row count, so
     its last bits vary with the number of envs)."""
@@ -92,23 +88,22 @@ def _x6_linear_padded(owner, name, x, w, b):
 
     N, Kd = w.shape
     Np, Kp = -(-N // 128) * 128, -(-Kd // 32) * 32
-    key = (w.data_ptr(), w._version, b.data_ptr(), b._version, Np, Kp)
-    cache = owner.__dict__.setdefault("_x6p", {})
-    ent = cache.get(name)
-    if ent is None or ent[0] != key:
+
+    def padded():
         wp = torch.zeros(Np, Kp, device=w.device, dtype=torch.float32)
         wp[:N, :Kd] = w.detach()
         bp = torch.zeros(Np, device=w.device, dtype=torch.float32)
         bp[:N] = b.detach()
-        ent = (key, K.pack_f32_weight(wp), bp)
-        cache[name] = ent
+        return K.pack_f32_weight(wp), bp
+
+    planes, bp = derived(owner, name, (w, b), padded)
     shp = x.shape
     x2 = x.reshape(-1, Kd)
     if Kp != Kd:
         xp = torch.zeros(x2.shape[0], Kp, device=x.device, dtype=torch.float32)
         xp[:, :Kd] = x2
         x2 = xp
-    return K.linear_f32x6(x2, ent[1], ent[2])[:, :N].reshape(*shp[:-1], N)
+    return K.linear_f32x6(x2, planes, bp)[:, :N].reshape(*shp[:-1], N)
 
 
 class MHA(nn.Module):
@@ -199,12 +194,8 @@ class _LayerOps(nn.Module):
             # the LayerNorm's pre-split rows in, the hidden layer kept in the pre-split form (scaled per
             # row by a Cauchy-Schwarz bound of its values): neither GEMM splits in registers
             l1, l2 = self.linear1, self.linear2
-            key = (l1.weight.data_ptr(), l1.weight._version, l1.bias.data_ptr(), l1.bias._version)
-            cache = self.__dict__.get("_ffn_bounds")
-            if cache is None or cache[0] != key:
-                cache = (key, K.weight_bounds(l1.weight, l1.bias))
-                self.__dict__["_ffn_bounds"] = cache
-            hs = K.linear_presplit_split(sp, _x6_planes(self, "linear1", l1.weight), l1.bias, cache[1], relu=True)
+            bounds = derived(self, "ffn_bounds", (l1.weight, l1.bias), lambda: K.weight_bounds(l1.weight, l1.bias))
+            hs = K.linear_presplit_split(sp, _x6_planes(self, "linear1", l1.weight), l1.bias, bounds, relu=True)
             return K.linear_presplit(hs, _x6_planes(self, "linear2", l2.weight), l2.bias).view(*x.shape[:-1], -1)
         if self.fused and _x6_ok(x, self.linear1.out_features) and self.linear2.out_features % 128 == 0:
             h = _x6_linear(self, "linear1", x, self.linear1.weight, self.linear1.bias, relu=True)
@@ -217,13 +208,9 @@ class _LayerOps(nn.Module):
 
     @staticmethod
     def _norm_f32(norm):
-        """The LayerNorm's weight/bias widened to f32 for the rmbx kernel (cached per storage)."""
-        key = (norm.weight.data_ptr(), norm.weight.dtype)
-        cache = norm.__dict__.get("_f32")
-        if cache is None or cache[0] != key:
-            cache = (key, norm.weight.detach().float().contiguous(), norm.bias.detach().float().contiguous())
-            norm.__dict__["_f32"] = cache
-        return cache[1], cache[2]
+        """The LayerNorm's weight/bias widened to f32 for the rmbx kernel."""
+        return derived(norm, "f32", (norm.weight, norm.bias), lambda: (
+            norm.weight.detach().float().contiguous(), norm.bias.detach().float().contiguous()))
 
     @staticmethod
     def _presplit(x):
@@ -368,19 +355,16 @@ class ActModel(nn.Module):
         D = mem.shape[2]
         ws = [l.multihead_attn.in_proj_weight for l in layers]
         bs = [l.multihead_attn.in_proj_bias for l in layers]
-        key = tuple((w.data_ptr(), w.dtype) for w in ws)
-        cache = self.__dict__.get("_cross_w")
-        if cache is None or cache[0] != key:
-            wk = torch.cat([w[D: 2 * D] for w in ws]).contiguous()
-            bk = torch.cat([b[D: 2 * D] for b in bs]).contiguous()
-            wv = torch.cat([w[2 * D:] for w in ws]).contiguous()
-            bv = torch.cat([b[2 * D:] for b in bs]).contiguous()
-            cache = (key, wk, bk, wv, bv)
-            self.__dict__["_cross_w"] = cache
-        _, wk, bk, wv, bv = cache
+
+        def concat():
+            return (torch.cat([w[D: 2 * D] for w in ws]).contiguous(), torch.cat([b[D: 2 * D] for b in bs]).contiguous(),
+                    torch.cat([w[2 * D:] for w in ws]).contiguous(), torch.cat([b[2 * D:] for b in bs]).contiguous())
+
+        wk, bk, wv, bv = derived(self, "cross_w", ws + bs, concat, extra=D)
         if _x6_ok(mem, wk.shape[0]):
-            k_all = _x6_linear(self, "cross_k", mem_pos, wk, bk)
-            v_all = _x6_linear(self, "cross_v", mem, wv, bv)
+            # (the planes are derived from the layers' parameters too, not from the concatenated copies)
+            k_all = _x6_linear(self, "cross_k", mem_pos, wk, bk, sources=ws)
+            v_all = _x6_linear(self, "cross_v", mem, wv, bv, sources=ws)
         else:
             k_all = F.linear(mem_pos, wk, bk)
             v_all = F.linear(mem, wv, bv)

@@ -18,6 +18,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ..derived import derived
+
 
 class SinusoidalPosEmb(nn.Module):
     def __init__(self, dim):
@@ -35,18 +37,12 @@ class SinusoidalPosEmb(nn.Module):
 def _gemm(owner, name, x2, w2, bias):
     """F.linear(x2, w2, bias) with w2 derived from owner.weight; f32 on the device through
     rmbx_linear_f32x6 (fp32-accurate bf16x6 GEMM) where the shape allows, with w2's bf16 pieces
-    cached on `owner` per version of owner.weight."""
+    held on `owner` (derived from owner.weight)."""
     from ... import kernels as K
 
     if x2.is_cuda and x2.dtype == torch.float32 and K.linear_f32x6_supported(x2, w2.shape[0]):
-        src = owner.weight
-        key = (src.data_ptr(), src._version, tuple(w2.shape))
-        cache = owner.__dict__.setdefault("_x6", {})
-        ent = cache.get(name)
-        if ent is None or ent[0] != key:
-            ent = (key, K.pack_f32_weight(w2.detach().contiguous()))
-            cache[name] = ent
-        return K.linear_f32x6(x2, ent[1], bias)
+        planes = derived(owner, name, (owner.weight,), lambda: K.pack_f32_weight(w2.detach().contiguous()))
+        return K.linear_f32x6(x2, planes, bias)
     return F.linear(x2, w2, bias)
 
 

@@ -21,6 +21,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ..derived import derived
 from ..diffusion.schedulers import DDIMSampler, DDPMSampler
 from ..diffusion.unet1d import ConditionalUnet1D
 
@@ -38,19 +39,13 @@ def _conv(conv, x):
     # (torch's GroupNorm hands back NCHW-contiguous tensors: re-lay them out, a memory-bound copy)
     x = x.contiguous(memory_format=torch.channels_last)
     w = conv.weight
-    key = (w.data_ptr(), w._version)
-    cache = conv.__dict__.get("_rmbx")
     if K.conv2d_f32x6_supported(conv.in_channels, conv.out_channels) and conv.stride[0] == conv.stride[1]:
-        if cache is None or cache[0] != key:
-            cache = (key, K.pack_conv_f32x6(w))
-            conv.__dict__["_rmbx"] = cache
-        return K.conv2d_f32x6(x, cache[1], None, conv.kernel_size, conv.stride[0], conv.padding[0])
+        planes = derived(conv, "x6", (w,), lambda: K.pack_conv_f32x6(w))
+        return K.conv2d_f32x6(x, planes, None, conv.kernel_size, conv.stride[0], conv.padding[0])
     if (conv.in_channels == conv.out_channels == 64 and tuple(conv.kernel_size) == (3, 3) and conv.stride[0] == 1
             and conv.padding[0] == 1):
-        if cache is None or cache[0] != key:
-            cache = (key, (K.pack_winograd4_f32(w), torch.zeros(64, device=w.device)))
-            conv.__dict__["_rmbx"] = cache
-        return K.conv3x3_winograd4_f32(x, cache[1][0], cache[1][1])
+        u, zero = derived(conv, "wino4", (w,), lambda: (K.pack_winograd4_f32(w), torch.zeros(64, device=w.device)))
+        return K.conv3x3_winograd4_f32(x, u, zero)
     if conv.in_channels <= 4 and conv.out_channels % 16 == 0 and conv.stride[0] == conv.stride[1] \
             and conv.padding[0] == conv.padding[1]:
         return K.conv2d_direct_f32(x, w, conv.bias, conv.stride[0], conv.padding[0])
@@ -116,18 +111,17 @@ class SpatialSoftmax(nn.Module):
             return c(f)
         f = f.contiguous(memory_format=torch.channels_last)
         w = c.weight
-        key = (w.data_ptr(), w._version)
-        cache = self.__dict__.get("_x6")
-        if cache is None or cache[0] != key:
+
+        def padded():
             n_pad = -(-c.out_channels // 128) * 128
             wp = torch.zeros(n_pad, c.in_channels, dtype=torch.float32, device=w.device)
             wp[: c.out_channels] = w.detach().reshape(c.out_channels, -1)
             bp = torch.zeros(n_pad, dtype=torch.float32, device=w.device)
             bp[: c.out_channels] = c.bias.detach()
-            cache = (key, K.pack_f32_weight(wp), bp)
-            self.__dict__["_x6"] = cache
-        B, C, H, W = f.shape
-        y = K.linear_f32x6(f.permute(0, 2, 3, 1), cache[1], cache[2])[..., : c.out_channels]  # [B, H, W, kp]
+            return K.pack_f32_weight(wp), bp
+
+        planes, bp = derived(self, "keypoints", (w, c.bias), padded)
+        y = K.linear_f32x6(f.permute(0, 2, 3, 1), planes, bp)[..., : c.out_channels]  # [B, H, W, kp]
         return y.permute(0, 3, 1, 2)
 
     def forward(self, f):
