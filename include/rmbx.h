@@ -720,6 +720,44 @@ int rmbx_pointcloud_fps(const float* depth, const uint8_t* rgb, int n_env, int H
                         const double* norm_c, float* out, double* raw, int32_t* count,
                         void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * SARNN policy step, batched over envs (policy/sarnn/SarnnPolicy.py:133-152 for the branch that
+ * reaches predicted_state: attention encoders, spatial softmax, LSTM cell, state decoder).
+ *
+ * rmbx_sarnn_attention: per (env, camera) the attention encoder Conv2d(3,16,3) -> LeakyReLU(0.3)
+ * -> Conv2d(16,32,3) -> LeakyReLU -> Conv2d(32,K,3) -> LeakyReLU -> SpatialSoftmax(temperature,
+ * normalized), fused: the feature maps live in LDS only (row bands with a 6-row input halo, an
+ * online max / sum merge of the softmax across bands inside the workgroup).  f32 FMA throughout;
+ * the result does not depend on n_env and is reproducible run to run.
+ *   images f32 [n_env][ncam][3][S][S] in [0, 1]
+ *   w1 f32 [ncam][2][3][9][8], b1 [ncam][16]; w2 [ncam][4][16][9][8], b2 [ncam][32];
+ *   w3 [ncam][G][32][9][g], b3 [ncam][K]: one set per camera; a packed weight is
+ *   [group][cin][ky*3+kx][channel in group] of the torch Conv2d weight [cout][cin][3][3] with the
+ *   output channels in consecutive groups (zero beyond cout), so the channels a wave computes
+ *   together are adjacent.  Groups hold 8 channels; for the last layer G = (K + 7) / 8 and
+ *   g = ceil(K / G) rounded up to even (kernels.sarnn_pack_attention builds all six)
+ *   keys f32 [n_env][ncam][K][2] = (sum pos_x att, sum pos_y att), pos_x = col / (S-7),
+ *   pos_y = row / (S-7), att = softmax(map / temperature) over the (S-6)^2 map
+ * Supported: 8 <= S <= 128, 1 <= K <= 16, 1 <= ncam <= 4, temperature > 0.
+ *
+ * rmbx_sarnn_lstm_step: torch.nn.LSTMCell (gate order i, f, g, o; c' = sig(f) c + sig(i) tanh(g),
+ * h' = sig(o) tanh(c')) on x = [state, keys] followed by the state decoder Linear(hidden, state_dim).
+ *   state f32 [n_env][state_dim]; keys f32 [n_env][key_dim] (camera-major, as rmbx_sarnn_attention
+ *   writes them); h, c f32 [n_env][hidden], updated in place
+ *   w_ih f32 [4 hidden][state_dim + key_dim], w_hh [4 hidden][hidden], b_ih, b_hh [4 hidden]
+ *   w_dec f32 [state_dim][hidden], b_dec [state_dim]
+ *   active u8 [n_env]: 0 = h, c and pred of that env untouched; NULL = all active
+ *   pred f32 [n_env][state_dim]
+ * Supported: 1 <= hidden <= 128, 1 <= state_dim, state_dim + key_dim <= 256, key_dim >= 0.
+ * ------------------------------------------------------------------------------------------- */
+int rmbx_sarnn_attention(const float* images, const float* w1, const float* b1, const float* w2,
+                         const float* b2, const float* w3, const float* b3, float* keys, int n_env,
+                         int ncam, int S, int K, float temperature, void* stream);
+int rmbx_sarnn_lstm_step(const float* state, const float* keys, float* h, float* c,
+                         const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                         const float* w_dec, const float* b_dec, const uint8_t* active, float* pred,
+                         int n_env, int state_dim, int key_dim, int hidden, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -117,6 +117,8 @@ SIGNATURES = {
     "rmbx_resize_f32": (_c_int, [_c_p, _c_p] + [_c_int] * 5 + [_c_p]),
     "rmbx_pointcloud_fps": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_int, _c_d, _c_p, _c_p, _c_int, _c_int,
                                      _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
+    "rmbx_sarnn_attention": (_c_int, [_c_p] * 8 + [_c_int] * 4 + [ctypes.c_float, _c_p]),
+    "rmbx_sarnn_lstm_step": (_c_int, [_c_p] * 12 + [_c_int] * 4 + [_c_p]),
 }
 
 

@@ -18,7 +18,7 @@ import sys
 
 import yaml
 
-POLICIES = ["Mlp", "Act", "DiffusionPolicy", "DiffusionPolicy3d"]
+POLICIES = ["Mlp", "Act", "DiffusionPolicy", "DiffusionPolicy3d", "Sarnn"]
 ENVS = ["MujocoUR5eCable", "MujocoUR5eInsert", "MujocoUR5eDoor", "MujocoUR5eCabinet", "MujocoUR5eToolbox", "MujocoUR5ePick",
         "MujocoUR5eRing"]
 
@@ -81,7 +81,7 @@ def main(argv=None):
     if int(os.environ.get("WORLD_SIZE", 1)) > 1:
         shard, n_envs = _shard_args(n_envs)
         remaining = remaining + shard  # argparse takes the last --num_envs: this rank's shard
-    if n_envs >= 256 and args.policy in ("Act", "Mlp"):
+    if n_envs >= 256 and args.policy in ("Act", "Mlp", "Sarnn"):
         # large conv batches: keep MIOpen Find from timing its naive reference solver (seconds per
         # shape, never selected); process-wide, read by MIOpen on first use
         os.environ.setdefault("MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_FWD", "0")

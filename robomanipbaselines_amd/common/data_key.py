@@ -55,6 +55,16 @@ class DataKey:
             return 3
         raise ValueError(f"[{cls.__name__}] Invalid data key: {key}")
 
+    @classmethod
+    def get_command_key(cls, key):
+        """DataKey.get_command_key (:163-170): the command key of a measured key (a command key is
+        its own)."""
+        if key.startswith("command_"):
+            return key
+        if key.startswith("measured_"):
+            return "command_" + key[len("measured_"):]
+        raise ValueError(f"[{cls.__name__}] Invalid data key: {key}")
+
 
 # include/rmbx.h RMBX_KEY_*: the state keys MotionManager.get_data serves for a UR5e env
 # (MotionManager.py:41-130; the *_rel measured keys fall through to its ValueError, and the UR5e

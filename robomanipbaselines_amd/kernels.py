@@ -1342,3 +1342,97 @@ def conv2d_direct_f32(x, weight, bias, stride=1, padding=0):
     N.call("rmbx_conv2d_direct_f32", N.ptr(x), n, h, w_, c, N.ptr(wp), N.ptr(bias), N.ptr(out), co, kh, kw, stride,
            padding, N.stream_ptr())
     return out
+
+
+# ------------------------------------------------------------------------------------------
+# SARNN policy step
+# ------------------------------------------------------------------------------------------
+def sarnn_supported(image_size, num_attentions, num_images, state_dim, hidden_dim):
+    """Whether rmbx_sarnn_attention / rmbx_sarnn_lstm_step serve this configuration (the ranges
+    include/rmbx.h states)."""
+    return (8 <= image_size <= 128 and 1 <= num_attentions <= 16 and 1 <= num_images <= 4 and 1 <= hidden_dim <= 128
+            and state_dim >= 1 and state_dim + num_images * num_attentions * 2 <= 256)
+
+
+def sarnn_conv_groups(cout):
+    """(groups, group size) of a packed SARNN conv: 8 output channels per group, or, for the last conv's
+    K <= 16 channels, (K + 7) // 8 equal groups rounded up to an even size (include/rmbx.h)."""
+    if cout % 8 == 0:
+        return cout // 8, 8
+    g = (cout + 7) // 8
+    return g, (-(-cout // g) + 1) & ~1
+
+
+def sarnn_pack_attention(convs):
+    """convs = per layer (3 layers) the list of per-camera Conv2d modules of the attention encoders ->
+    (w1, b1, w2, b2, w3, b3) as rmbx_sarnn_attention reads them: weights [ncam, groups, cin, 9, ocg]
+    (the output channel fastest, zero beyond cout), biases [ncam, cout]."""
+    out = []
+    for layer in convs:
+        w = torch.stack([m.weight.detach() for m in layer]).float()  # [ncam, cout, cin, 3, 3]
+        ncam, cout, cin = w.shape[:3]
+        g, ocg = sarnn_conv_groups(cout)
+        wp = torch.zeros((ncam, g * ocg, cin, 9), dtype=torch.float32, device=w.device)
+        wp[:, :cout] = w.reshape(ncam, cout, cin, 9)
+        out.append(wp.view(ncam, g, ocg, cin, 9).permute(0, 1, 3, 4, 2).contiguous())
+        out.append(torch.stack([m.bias.detach() for m in layer]).float().contiguous())
+    return tuple(out)
+
+
+def sarnn_attention(images, packed, temperature, out=None):
+    """images f32 [n, ncam, 3, S, S] -> attention points f32 [n, ncam, K, 2] (rmbx_sarnn_attention).
+    packed = sarnn_pack_attention(...) of the attention encoders' conv parameters."""
+    _chk(images, torch.float32, name="images")
+    if images.dim() != 5 or images.shape[2] != 3 or images.shape[3] != images.shape[4]:
+        raise ValueError(f"images must be [n, ncam, 3, S, S] (got {tuple(images.shape)})")
+    n, ncam, _, S, _ = images.shape
+    w1, b1, w2, b2, w3, b3 = packed
+    _chk(b3, torch.float32, name="b3")
+    k = b3.shape[1] if b3.dim() == 2 else -1
+    if not 1 <= k <= 16:
+        raise ValueError(f"b3 must be [ncam, K] with 1 <= K <= 16 (got {tuple(b3.shape)})")
+    g3, ocg3 = sarnn_conv_groups(k)
+    for t, shape, nm in ((w1, (ncam, 2, 3, 9, 8), "w1"), (b1, (ncam, 16), "b1"), (w2, (ncam, 4, 16, 9, 8), "w2"),
+                         (b2, (ncam, 32), "b2"), (w3, (ncam, g3, 32, 9, ocg3), "w3"), (b3, (ncam, k), "b3")):
+        _chk(t, torch.float32, shape, nm)
+        if t.device != images.device:
+            raise ValueError(f"{nm} is on {t.device}, images on {images.device}")
+    if out is None:
+        out = torch.empty((n, ncam, k, 2), dtype=torch.float32, device=images.device)
+    _chk(out, torch.float32, (n, ncam, k, 2), "out")
+    if out.device != images.device:
+        raise ValueError(f"out is on {out.device}, images on {images.device}")
+    N.call("rmbx_sarnn_attention", N.ptr(images), N.ptr(w1), N.ptr(b1), N.ptr(w2), N.ptr(b2), N.ptr(w3), N.ptr(b3),
+           N.ptr(out), n, ncam, S, k, float(temperature), N.stream_ptr())
+    return out
+
+
+def sarnn_lstm_step(state, keys, h, c, w_ih, w_hh, b_ih, b_hh, w_dec, b_dec, active=None, out=None):
+    """torch LSTMCell on [state, keys] + the state decoder (rmbx_sarnn_lstm_step): state f32 [n, S],
+    keys f32 [n, Kd], h / c f32 [n, Hd] updated in place, active u8 [n] (0 = env untouched) ->
+    predicted state f32 [n, S]."""
+    _chk(state, torch.float32, name="state")
+    _chk(keys, torch.float32, name="keys")
+    if state.dim() != 2 or keys.dim() != 2 or keys.shape[0] != state.shape[0]:
+        raise ValueError(f"state must be [n, S] and keys [n, Kd] (got {tuple(state.shape)}, {tuple(keys.shape)})")
+    n, sd = state.shape
+    kd = keys.shape[1]
+    _chk(h, torch.float32, name="h")
+    hd = h.shape[1] if h.dim() == 2 else -1
+    _chk(h, torch.float32, (n, hd), "h")
+    _chk(c, torch.float32, (n, hd), "c")
+    for t, shape, nm in ((w_ih, (4 * hd, sd + kd), "w_ih"), (w_hh, (4 * hd, hd), "w_hh"), (b_ih, (4 * hd,), "b_ih"),
+                         (b_hh, (4 * hd,), "b_hh"), (w_dec, (sd, hd), "w_dec"), (b_dec, (sd,), "b_dec")):
+        _chk(t, torch.float32, shape, nm)
+    if active is not None:
+        _chk(active, torch.uint8, (n,), "active")
+    if out is None:
+        out = torch.empty((n, sd), dtype=torch.float32, device=state.device)
+    _chk(out, torch.float32, (n, sd), "out")
+    for t, nm in ((keys, "keys"), (h, "h"), (c, "c"), (w_ih, "w_ih"), (w_hh, "w_hh"), (b_ih, "b_ih"), (b_hh, "b_hh"),
+                  (w_dec, "w_dec"), (b_dec, "b_dec"), (active, "active"), (out, "out")):
+        if t is not None and t.device != state.device:
+            raise ValueError(f"{nm} is on {t.device}, state on {state.device}")
+    N.call("rmbx_sarnn_lstm_step", N.ptr(state), N.ptr(keys), N.ptr(h), N.ptr(c), N.ptr(w_ih), N.ptr(w_hh), N.ptr(b_ih),
+           N.ptr(b_hh), N.ptr(w_dec), N.ptr(b_dec), N.ptr(active), N.ptr(out), n, sd, kd, hd, N.stream_ptr())
+    return out
