@@ -178,6 +178,97 @@ int rmbx_sched_update(rmbx_sched_t* sched, const double* time, const double* rew
  * transition step's, as the reference's saved image is. */
 int rmbx_sched_active(const rmbx_sched_t* sched, int n_pre, uint8_t* active, int n_env, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Episode streaming: a fixed batch of n_env slots works through a queue of n_episodes >= n_env
+ * episodes (--num_episodes).  A slot whose episode has finished is recorded, given the next
+ * episode of the queue and re-armed on the device; the host never learns which slots those were.
+ * The caller launches the recycle only at the end of env-steps g with (g + 1) % P == 0, P = skip
+ * x the policy's inference period: every episode then starts on a multiple of P, spends the same
+ * clock-driven number of steps before RolloutPhase, and so shares the host's skip / inference
+ * phase (rollout_time_idx of every slot == the host's global rollout index mod P).
+ * Plain C++: one workgroup, no atomics, vector stores only.
+ *
+ * rmbx_sched_phases: phase[e] = sched[e].phase, entered[e] = (phase[e] != prev_phase[e]), then
+ * prev_phase[e] = phase[e].  Called once per env-step after rmbx_sched_update (and after the
+ * recycle on the steps that have one, so a re-armed slot reports phase 0 as entered).
+ *
+ * rmbx_sched_close_bad: the engine's divergence guard (rmbx_env_buffers.stats[3]) rewinds a
+ * slot's clock to 0 in mid-episode, which would break the alignment above; in streaming mode such
+ * an episode is closed at once.  For every slot that is not done: bad_resets[e] > 0 -> done = 1,
+ * phase = n_pre + 1, success = 0, result_reward = 0, duration = last_elapsed[e] (its RolloutPhase
+ * time at the last step before the rewind, 0 in the earlier phases); otherwise last_elapsed[e] is
+ * brought up to date (time - phase_start in RolloutPhase, else 0).  Called after
+ * rmbx_sched_update.
+ *
+ * rmbx_episode_recycle, for every slot with sched.done set and an episode (slot_episode >= 0):
+ *  (a) record  results[episode - episode_base] = {episode, slot, world_idx, rollout_time_idx,
+ *      success, bad_state = bad_resets > 0, reward = result_reward, duration}; with final_qpos,
+ *      final_qpos[episode - episode_base] = the slot's qpos row
+ *  (b) assign  the next episodes of the queue to the finished slots in increasing slot order
+ *      (exclusive prefix sum of the done flags over chunks of 256 slots with a running base: the
+ *      slot -> episode map is reproducible)
+ *  (c) re-arm  schedule as rmbx_sched_reset at time 0; engine time = 0, qpos = qpos0, qvel =
+ *      qacc_ws = 0, ctrl = ctrl0, stats = 0; q_cmd / target_R / target_p = motion0 (the initial
+ *      arm pose and its constant FK), grip_cmd = 0; bad_resets = 0, last_elapsed = 0; the
+ *      episode's world position world_pos[episode - episode_base] to body_pos[slot][world_body]
+ *      (world_body >= 0) or qpos[slot][world_qadr .. +3] (world_qadr >= 0, a free body), or
+ *      nowhere (both < 0)
+ *  (d) publish slot_episode[slot] = the new episode, recycled[slot] = 1, counters = {next local
+ *      episode, finished episodes}.
+ * With the queue empty a done slot is recorded, slot_episode[slot] = -1 (so it is never recorded
+ * twice) and its state is left frozen.  recycled[e] is written (0 / 1) for every slot; nothing
+ * else of a slot that is not done is written.  The caller then runs rmbx_engine_forward with
+ * active = recycled.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct rmbx_episode_record_t {
+  int32_t episode;          /* global episode index */
+  int32_t slot;             /* env slot it ran in */
+  int32_t world_idx;
+  int32_t rollout_time_idx;
+  uint8_t success;
+  uint8_t bad_state;        /* closed by the divergence guard */
+  uint8_t pad_[6];
+  double reward;
+  double duration;
+} rmbx_episode_record_t;
+
+/* Host struct of device pointers (read during the call only). */
+typedef struct rmbx_stream_buffers {
+  rmbx_sched_t* sched;            /* [n_env] */
+  int32_t* slot_episode;          /* [n_env] global episode in each slot, -1 = none */
+  uint8_t* recycled;              /* [n_env] out */
+  int32_t* counters;              /* [2] {next local episode, finished} */
+  rmbx_episode_record_t* results; /* [n_episodes] */
+  double* final_qpos;             /* [n_episodes][nq] or NULL */
+  const int32_t* world_idx;       /* [n_episodes] */
+  const double* world_pos;        /* [n_episodes][3] */
+  double* time;                   /* engine state, as rmbx_env_buffers */
+  double* qpos;
+  double* qvel;
+  double* qacc_ws;
+  double* ctrl;                   /* [n_env][ctrl_stride] */
+  double* body_pos;
+  int32_t* stats;                 /* [n_env][4] */
+  const double* qpos0;            /* [nq] initial qpos (world position of a free body aside) */
+  const double* ctrl0;            /* [nu] */
+  double* q_cmd;                  /* [n_env][6] */
+  double* grip_cmd;               /* [n_env] */
+  double* target_R;               /* [n_env][9] */
+  double* target_p;               /* [n_env][3] */
+  const double* motion0;          /* [18] q_cmd(6), target_R(9), target_p(3) of the initial pose */
+  int32_t* bad_resets;            /* [n_env] */
+  double* last_elapsed;           /* [n_env] */
+  int32_t n_env, n_episodes, episode_base;
+  int32_t nq, nv, nu, ctrl_stride, nbody;
+  int32_t world_body, world_qadr;
+} rmbx_stream_buffers;
+
+int rmbx_sched_phases(const rmbx_sched_t* sched, int32_t* prev_phase, int32_t* phase, uint8_t* entered,
+                      int n_env, void* stream);
+int rmbx_sched_close_bad(rmbx_sched_t* sched, const double* time, const int32_t* bad_resets,
+                         double* last_elapsed, int n_pre, int n_env, void* stream);
+int rmbx_episode_recycle(const rmbx_stream_buffers* bufs, void* stream);
+
 
 /* ---------------------------------------------------------------------------------------------
  * Batched MuJoCo-subset physics engine (the env.step hot path).

@@ -41,6 +41,9 @@ SIGNATURES = {
     "rmbx_sched_reset": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_p]),
     "rmbx_sched_active": (_c_int, [_c_p, _c_int, _c_p, _c_int, _c_p]),
     "rmbx_sched_update": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_d, _c_d, _c_int, _c_p]),
+    "rmbx_sched_phases": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_p]),
+    "rmbx_sched_close_bad": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_p]),
+    "rmbx_episode_recycle": (_c_int, [_c_p, _c_p]),
     "rmbx_engine_create": (_c_int, [_c_p, _c_int, _c_p]),
     "rmbx_engine_destroy": (_c_int, [_c_p]),
     "rmbx_engine_workspace_bytes": (_c_int, [_c_p, _c_p]),
@@ -153,6 +156,18 @@ class EnvBuffers(ctypes.Structure):
     _fields_ = [(n, _c_p) for n in ("time", "qpos", "qvel", "qacc_ws", "ctrl", "body_pos", "xpos", "xquat",
                                     "gxpos", "gxmat", "sensordata", "stats", "workspace")]
 
+
+class StreamBuffers(ctypes.Structure):
+    """ctypes mirror of rmbx_stream_buffers (include/rmbx.h)."""
+
+    _fields_ = ([(n, _c_p) for n in ("sched", "slot_episode", "recycled", "counters", "results", "final_qpos",
+                                     "world_idx", "world_pos", "time", "qpos", "qvel", "qacc_ws", "ctrl", "body_pos",
+                                     "stats", "qpos0", "ctrl0", "q_cmd", "grip_cmd", "target_R", "target_p",
+                                     "motion0", "bad_resets", "last_elapsed")]
+                + [(n, ctypes.c_int32) for n in ("n_env", "n_episodes", "episode_base", "nq", "nv", "nu",
+                                                 "ctrl_stride", "nbody", "world_body", "world_qadr")])
+
+
 # numpy mirror of rmbx_sched_t (include/rmbx.h)
 TEX_LEVELS = 16  # include/rmbx.h RMBX_TEX_LEVELS
 
@@ -171,6 +186,22 @@ SCHED_DTYPE = np.dtype(
     ]
 )
 assert SCHED_DTYPE.itemsize == 48
+
+# numpy mirror of rmbx_episode_record_t (include/rmbx.h)
+EPISODE_DTYPE = np.dtype(
+    [
+        ("episode", np.int32),
+        ("slot", np.int32),
+        ("world_idx", np.int32),
+        ("rollout_time_idx", np.int32),
+        ("success", np.uint8),
+        ("bad_state", np.uint8),
+        ("pad_", np.uint8, 6),
+        ("reward", np.float64),
+        ("duration", np.float64),
+    ]
+)
+assert EPISODE_DTYPE.itemsize == 40
 
 _lib = None
 

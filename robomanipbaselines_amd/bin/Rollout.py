@@ -9,6 +9,10 @@ order matters, :82-86); remaining arguments go to the inner parser.
 torch.distributed.run), each stepping the contiguous global env range of its rank
 (distributed.shard_range; world index and noise stream per GLOBAL env), then one RCCL all-gather
 of the per-env results; rank 0 prints them and writes the YAML in global env order.
+
+--num_episodes M: streaming mode (rollout_base.run_streaming): min(--num_envs, M) env slots work
+through M episodes; with --num_gpus each rank takes a contiguous range of the episode queue and
+rank 0 reports all M in global episode order.
 """
 
 import argparse
@@ -76,10 +80,14 @@ def main(argv=None):
     pre.add_argument("--num_envs", type=int, default=None)
     pre.add_argument("--world_idx_list", type=int, nargs="*", default=None)
     pre.add_argument("--world_idx", type=int, default=0)
+    pre.add_argument("--num_episodes", type=int, default=None)
+    pre.add_argument("--episode_offset", type=int, default=0)
     ns, _ = pre.parse_known_args(remaining)
     n_envs = ns.num_envs or len(ns.world_idx_list or [ns.world_idx])
+    if ns.num_episodes is not None:
+        n_envs = min(n_envs, ns.num_episodes)
     if int(os.environ.get("WORLD_SIZE", 1)) > 1:
-        shard, n_envs = _shard_args(n_envs)
+        shard, n_envs = _shard_args(n_envs, ns.num_episodes, ns.episode_offset)
         remaining = remaining + shard  # argparse takes the last --num_envs: this rank's shard
     if n_envs >= 256 and args.policy in ("Act", "Mlp", "Sarnn"):
         # large conv batches: keep MIOpen Find from timing its naive reference solver (seconds per
@@ -94,20 +102,31 @@ def main(argv=None):
     return rollout
 
 
-def _shard_args(total):
+def shard_overrides(rank, world, total, num_episodes=None, episode_offset=0):
+    """Inner-parser overrides of rank `rank` of `world`: its contiguous env range, and with
+    --num_episodes its contiguous range of the episode queue (the env shard are its slots)."""
+    from ..distributed import shard_range
+
+    g0, g1 = shard_range(rank, world, total)
+    out = ["--num_envs", str(g1 - g0), "--env_offset", str(g0)]
+    if num_episodes is not None:
+        e0, e1 = shard_range(rank, world, num_episodes)
+        out += ["--num_episodes", str(e1 - e0), "--episode_offset", str(episode_offset + e0)]
+    return out, g1 - g0
+
+
+def _shard_args(total, num_episodes=None, episode_offset=0):
     """Join this rank's process group (RCCL); return the inner-parser overrides of its shard and
     the shard's env count."""
     import torch
     import torch.distributed as dist
 
-    from ..distributed import shard_range
-
     rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
     local = int(os.environ.get("LOCAL_RANK", rank))
     torch.cuda.set_device(local)
     dist.init_process_group("nccl", device_id=torch.device(f"cuda:{local}"))
-    g0, g1 = shard_range(rank, world, total)
-    return ["--num_envs", str(g1 - g0), "--env_offset", str(g0), "--device", f"cuda:{local}"], g1 - g0
+    shard, n_local = shard_overrides(rank, world, total, num_episodes, episode_offset)
+    return shard + ["--device", f"cuda:{local}"], n_local
 
 
 def _rank_entry(local_rank, world, port, argv):

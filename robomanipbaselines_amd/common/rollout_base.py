@@ -14,6 +14,12 @@ semantics, results schema) for a batch of envs:
 * results: {"success": [...], "reward": [...], "duration": [...]} per env in env order, the
   `Rollout result: success|failure` stdout contract (RolloutBase.py:96-107) and the optional
   YAML file (RolloutBase.py:417-422); inference-duration statistics (RolloutBase.py:528-539).
+* streaming (--num_episodes M, run_streaming / step_stream): the n envs are slots that work through
+  a queue of M >= n episodes; a finished slot is recorded, given the next episode and re-armed on
+  the device (rmbx_episode_recycle) at the end of steps aligned to P = skip x the policy's
+  inference period, so every slot keeps the host's skip / inference phase and the policy runs on
+  all n rows at the lockstep shapes ("Streaming").  Results: M entries in episode
+  order.  The lockstep entry points (run, step_once, reset) are untouched by it.
 """
 
 import argparse
@@ -120,6 +126,15 @@ class BatchedRolloutBase:
         parser.add_argument("--env_offset", type=int, default=0,
                             help="global index of local env 0 (this rank's shard start under --num_gpus): world "
                                  "indices and noise streams follow the global env index")
+        parser.add_argument("--num_episodes", type=int, default=None,
+                            help="streaming mode: evaluate this many episodes on min(--num_envs, M) env slots; a "
+                                 "finished slot is recorded, reset and given the next episode on the device. "
+                                 "Episode i uses world_idx_list[i %% len] and the noise stream (seed, i), as env i "
+                                 "of a lockstep run does. Not with --save_last_image: a recycled slot no longer "
+                                 "holds its episode's last frame")
+        parser.add_argument("--episode_offset", type=int, default=0,
+                            help="global index of this process's first episode (its shard start under --num_gpus), "
+                                 "the role --env_offset plays for envs")
         if self.require_task_desc:
             parser.add_argument("--task_desc", type=str, required=True)
         self.set_additional_args(parser)
@@ -133,6 +148,16 @@ class BatchedRolloutBase:
         if self.args.world_random_scale is not None:
             self.args.world_random_scale = np.array(self.args.world_random_scale)
         self.args.auto_exit = True  # headless batched evaluation always auto-exits
+        if self.args.num_episodes is not None:
+            if self.args.num_episodes < 1:
+                raise ValueError("--num_episodes must be at least 1")
+            if self.args.save_last_image:
+                raise ValueError("--save_last_image cannot be combined with --num_episodes: a recycled env slot no "
+                                 "longer holds the last frame of the episodes it ran")
+            # the slots: never more than the episodes; slot e starts with episode episode_offset + e,
+            # which is what a lockstep reset gives env e at this env_offset
+            self.args.num_envs = min(self.args.num_envs, self.args.num_episodes)
+            self.args.env_offset = self.args.episode_offset
 
     def set_additional_args(self, parser):
         pass
@@ -382,7 +407,157 @@ class BatchedRolloutBase:
         K.sched_active(self.sched, len(self.pre_durations), out=self._step_mask)
         self._host_transition()
 
+    # -- streaming mode (--num_episodes): n slots work through a queue of M episodes -----------
+    # How many infer_policy() calls apart the policy reads a new observation for its action buffer
+    # (1: every call; the policies with an action buffer: its length)
+    infer_period_calls = 1
+
+    @property
+    def stream_period(self):
+        """P = skip x infer_period_calls env-steps: finished slots are recycled only at the end of
+        global steps g with (g + 1) % P == 0, so every episode starts on a multiple of P and shares
+        the host's skip / inference phase."""
+        return int(self.args.skip) * int(self.infer_period_calls)
+
+    def reset_policy_state(self, mask):
+        """Forget the episode of the slots of `mask` (u8 [n], device; no host sync): recurrent
+        state, ensemble ring, action buffer, observation history.  Defined by the policy."""
+        raise NotImplementedError(f"{self.__class__.__name__} does not define reset_policy_state")
+
+    def _fill_first_obs(self, hist, new, dim):
+        """Observation histories of the policies that keep n_obs_steps of them: the rows whose
+        episode has just begun (reset_policy_state) hold the new observation in every entry of
+        `dim`, as the reference's first call of an episode does; the other rows keep `hist`."""
+        first = getattr(self, "_first_obs", None)
+        if first is None:
+            return hist
+        return torch.where(first.view((self.n,) + (1,) * (hist.dim() - 1)), new.unsqueeze(dim), hist)
+
+    def _reset_obs_history(self, mask):
+        m = mask.bool()
+        first = getattr(self, "_first_obs", None)
+        self._first_obs = m if first is None else (first | m)
+
+    def _phase_entry_steps(self):
+        """N_k for k = 1 .. n_pre: the env-step count an episode has spent when it enters phase k
+        (k = n_pre: RolloutPhase), from the host mirror of the phase clock -- the same for every
+        episode, since the pre-rollout phases are clock-driven and every clock starts at 0."""
+        t, start, out = 0.0, 0.0, []
+        steps = 0
+        for dur in self.pre_durations:
+            while True:
+                for _ in range(self.env.frame_skip):
+                    t += self.env.sim_timestep
+                steps += 1
+                if t - start > dur:
+                    break
+            start = t
+            out.append(steps)
+        return out
+
+    def reset_streaming(self):
+        """Lockstep reset of the n slots as episodes episode_offset .. + n - 1, plus the episode
+        queue: the world table of this process's M episodes and the recycle buffers."""
+        a = self.args
+        self.reset()
+        env, eng = self.env, self.env.engine
+        M, g0 = int(a.num_episodes), int(a.episode_offset)
+        widx, wpos = env.world_table(g0 + np.arange(M), a.world_idx_list)
+        self._episode_world = np.asarray(widx, dtype=np.int64)
+        world_body, world_qadr = env.world_slot()
+        motion0 = torch.cat([self.q_cmd[0], self._tgt_R[0], self._tgt_p[0]]).cpu().numpy()  # constant FK
+        self.stream = K.EpisodeStream(
+            self.sched, eng, self.q_cmd, self.grip_cmd, self._tgt_R, self._tgt_p, env.bad_resets, env.init_qpos,
+            np.concatenate([env.init_qpos[:6], [0.0]])[: eng.nu], motion0, widx, wpos, episode_base=g0,
+            world_body=world_body, world_qadr=world_qadr, final_qpos=getattr(self, "record_final_qpos", False))
+        self.slot_episode = self.stream.slot_episode
+        self.stream.phases()
+        self._entry_steps = self._phase_entry_steps()
+        self._grip_values = {}
+        self._g = 0  # global env-step index
+        self.episode_records = None
+
+    def _reach_target(self, ph):
+        """(R [n, 9], p [n, 3]) a reach phase would set now for every slot."""
+        if ph.target is not None:
+            return ph.target(self)
+        end = self.env.get_body_pose("cable_end")[:, :3].clone()
+        end[:, 2] = ph.pos_z
+        R = torch.tensor([-1.0, 0, 0, 0, 1.0, 0, 0, 0, -1.0], dtype=torch.float64, device=self.device)
+        return R.expand(self.n, 9), end
+
+    def step_stream(self):
+        """One env-step of every slot, each in its own phase (the order of step_once); recycles the
+        finished slots when the step is aligned.  No host synchronisation."""
+        from .. import _native as N
+
+        st, n_pre, P, skip = self.stream, len(self.pre_durations), self.stream_period, self.args.skip
+        g, N_pre = self._g, self._entry_steps[-1]
+        self._mark("glue")
+        # 1. pre-motion phases, each under the mask of the slots that are in it
+        for k in range(1, n_pre):
+            ph = self.pre_phases[k - 1]
+            in_k = st.phase == k
+            if ph.kind == "reach":
+                N.call("rmbx_arm_ik", N.ptr(self._placement), N.ptr(self.q_cmd), N.ptr(self._tgt_R),
+                       N.ptr(self._tgt_p), N.ptr(in_k.to(torch.uint8)), self.n, 1, N.stream_ptr())
+            elif ph.kind == "grasp":
+                gv = self._ghi if ph.grip is None else (self._glo if ph.grip == "low" else float(ph.grip))
+                self.grip_cmd.copy_(torch.where(in_k[:, None], gv, self.grip_cmd))
+        # 2. RolloutPhase: the host's global rollout index is every slot's, mod P
+        hr = g - N_pre
+        if hr >= 0:
+            in_rollout = st.phase == n_pre
+            if hr % P == 0:
+                self.reset_policy_state((in_rollout & (st.entered != 0)).to(torch.uint8))
+            self.rollout_time_idx = hr
+            if hr % skip == 0:
+                self._timed_infer()
+            K.motion_command(self._placement, self.policy_action, self._action_codes, hr % skip != 0, self._glo,
+                             self._ghi, self.q_cmd, self.grip_cmd, self._tgt_R, self._tgt_p,
+                             mask=in_rollout.to(torch.uint8))
+        # 3. step + schedule
+        self.obs, self.reward, _, _, self.info = self.env.step(self.env_action(), active=self._step_mask)
+        K.sched_update(self.sched, self.env.get_time(), self.reward, self._pre, self.args.max_duration)
+        st.close_bad(n_pre)
+        K.sched_active(self.sched, n_pre, out=self._step_mask)
+        # 4. recycle on aligned steps, then the phase report
+        if (g + 1) % P == 0:
+            self._mark("recycle")
+            st.recycle()
+            K.sched_active(self.sched, n_pre, out=self._step_mask)
+            self.env.refresh(active=st.recycled)
+            self.obs, self.reward, self.info = self.env._get_obs(), self.env.reward, self.env._get_info()
+            self._mark("glue")
+        st.phases()
+        # reach targets of the slots that entered a reach phase with this step (a phase is entered
+        # N_k steps after an aligned episode start, so only on steps of one residue mod P)
+        for k in range(1, n_pre):
+            ph = self.pre_phases[k - 1]
+            if ph.kind == "reach" and g + 1 >= self._entry_steps[k - 1] and (g + 1 - self._entry_steps[k - 1]) % P == 0:
+                m = ((st.phase == k) & (st.entered != 0))[:, None]
+                R, p = self._reach_target(ph)
+                self._tgt_R.copy_(torch.where(m, R, self._tgt_R))
+                self._tgt_p.copy_(torch.where(m, p, self._tgt_p))
+        self._g = g + 1
+        self.rollout_time_idx = max(self._g - N_pre, 0)
+
+    def run_streaming(self, max_steps=None):
+        self.reset_streaming()
+        max_steps = max_steps or self.args.max_steps or 10**9
+        M, steps = int(self.args.num_episodes), 0
+        while steps < max_steps:
+            self.step_stream()
+            steps += 1
+            # the only host read of the loop: the two device counters, every 16 steps
+            if steps % 16 == 0 and int(self.stream.counters.cpu()[1]) >= M:
+                break
+        self.finish()
+        return steps
+
     def run(self, max_steps=None):
+        if self.args.num_episodes is not None:
+            return self.run_streaming(max_steps)
         self.reset()
         max_steps = max_steps or self.args.max_steps or 10**9
         steps = 0
@@ -409,6 +584,8 @@ class BatchedRolloutBase:
         """RolloutPhase / EndRolloutPhase result bookkeeping (RolloutBase.py:96-110, 417-422) for
         every env.  Under --num_gpus the per-env records of all shards are all-gathered (one RCCL
         all_gather, distributed.py) and rank 0 prints and writes them in global env order."""
+        if getattr(self.args, "num_episodes", None) is not None:
+            return self._finish_streaming()
         v = K.sched_view(self.sched)
         succ, rew, dur = v["success"].astype(bool), v["result_reward"].astype(np.float64), v["duration"]
         rank, world = self._dist_world()
@@ -433,6 +610,47 @@ class BatchedRolloutBase:
             with open(self.args.result_filename, "w") as f:
                 yaml.dump(self.result, f)
         if rank == 0:
+            self.print_statistics()
+
+    def _finish_streaming(self):
+        """finish() of a streaming run: one record per episode, in episode order.  An episode the
+        run was cut off before (--max_steps) is reported as a failure of duration 0 (its record's
+        `episode` is -1).  Under --num_gpus the ranks' contiguous episode shards are all-gathered
+        and rank 0 reports them in global episode order."""
+        rec = self.stream.records()
+        self.episode_records = rec
+        self.bad_state_episodes = int(rec["bad_state"].sum())
+        succ, rew, dur = rec["success"].astype(bool), rec["reward"].copy(), rec["duration"].copy()
+        nbad = self.bad_state_episodes
+        rank, world = self._dist_world()
+        if world > 1:
+            import torch.distributed as dist
+
+            from ..distributed import gather_results, pack_results
+
+            dev = self.device if dist.get_backend() == "nccl" else "cpu"
+            g = gather_results(pack_results(succ, rew, dur, rec["rollout_time_idx"]), dev)
+            h = gather_results(pack_results(rec["episode"], rec["slot"], rec["world_idx"], rec["bad_state"]), dev)
+            succ, rew, dur = g[:, 0] != 0, g[:, 1], g[:, 2]
+            nbad = int(h[:, 3].sum())
+            # every rank's episode_records: all episodes, in global episode order
+            from .. import _native as N
+
+            rec = np.zeros(len(g), dtype=N.EPISODE_DTYPE)
+            rec["success"], rec["reward"], rec["duration"], rec["rollout_time_idx"] = succ, rew, dur, g[:, 3]
+            rec["episode"], rec["slot"], rec["world_idx"], rec["bad_state"] = h[:, 0], h[:, 1], h[:, 2], h[:, 3]
+            self.episode_records = rec
+        if rank == 0:
+            for e in range(len(succ)):
+                print(f"Rollout result: {'success' if succ[e] else 'failure'}", flush=True)
+                self.result["success"].append(bool(succ[e]))
+                self.result["reward"].append(float(rew[e]))
+                self.result["duration"].append(float(dur[e]))
+            if self.args.result_filename is not None:
+                print(f"[{self.__class__.__name__}] Save the rollout results: {self.args.result_filename}")
+                with open(self.args.result_filename, "w") as f:
+                    yaml.dump(self.result, f)
+            self.bad_state_episodes = nbad
             self.print_statistics()
 
     def save_rgb_images(self, v=None):
@@ -465,5 +683,7 @@ class BatchedRolloutBase:
             a = np.array(self.inference_duration_list)
             print(f"  - Inference duration [s] | mean: {a.mean():.2e}, std: {a.std():.2e} min: {a.min():.2e}, max: {a.max():.2e}")
             print(f"  - Inference duration per env [us] | mean: {1e6 * a.mean() / self.n:.2f}")
+        if getattr(self.args, "num_episodes", None) is not None:
+            print(f"  - Episodes closed by a bad-state reset | {getattr(self, 'bad_state_episodes', 0)}")
         if torch.cuda.is_available():
             print(f"  - GPU memory usage [GB] | {torch.cuda.max_memory_reserved() / 1024**3:.3f}")

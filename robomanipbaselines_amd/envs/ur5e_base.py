@@ -26,6 +26,31 @@ ARM_JOINTS = ["shoulder_pan_joint", "shoulder_lift_joint", "elbow_joint", "wrist
 GRIPPER_JOINTS = ["right_driver_joint", "right_spring_link_joint", "left_driver_joint", "left_spring_link_joint"]
 
 
+def world_placements(seed, indices, world_idx, offsets, scale, origin=(0.0, 0.0, 0.0)):
+    """Task-body position [len(indices), 3] of the envs / episodes with the global `indices`:
+    origin + offsets[world_idx] plus, with `scale`, U(-scale, scale)^3 noise from the Philox stream
+    (seed, global index).  Pure numpy: no device, no env."""
+    offsets = np.asarray(offsets, dtype=np.float64)
+    world_idx = np.asarray(world_idx, dtype=np.int64)
+    pos = np.asarray(origin, dtype=np.float64)[None] + offsets[world_idx]
+    if scale is not None:
+        s = np.asarray(scale, dtype=np.float64)
+        for e, i in enumerate(indices):
+            rng = np.random.Generator(np.random.Philox(key=int(seed), counter=[int(i), 0, 0, 0]))
+            pos[e] += rng.uniform(low=-1.0 * s, high=s, size=3)
+    return pos
+
+
+def world_positions(seed, indices, world_idx_list, offsets, scale, origin=(0.0, 0.0, 0.0)):
+    """(world_idx, pos) of the global env / episode `indices`: index i uses the world
+    world_idx_list[i % len(world_idx_list)] (BatchedRolloutBase.reset) and the placement of
+    world_placements -- the identity of an episode, whatever slot, batch or GPU runs it."""
+    indices = np.asarray(indices, dtype=np.int64).reshape(-1)
+    wl = np.asarray(world_idx_list, dtype=np.int64).reshape(-1)
+    world_idx = wl[indices % len(wl)]
+    return world_idx, world_placements(seed, indices, world_idx, offsets, scale, origin)
+
+
 class BatchedMujocoUR5eEnvBase:
     sim_timestep = 0.004  # MujocoEnvBase.py:12
     frame_skip = 8  # MujocoEnvBase.py:13
@@ -97,17 +122,23 @@ class BatchedMujocoUR5eEnvBase:
         """Per-env world index and task-body position: offset per world index plus U(-s, s)^3
         noise from a per-env Philox stream (seed, global env index = env_offset + local index)."""
         n = self.num_envs
-        offsets = np.asarray(self.world_offsets, dtype=np.float64)
         if world_idx is None:
-            world_idx = np.asarray(cumulative_idx) % len(offsets)
+            world_idx = np.asarray(cumulative_idx) % len(self.world_offsets)
         world_idx = np.broadcast_to(np.asarray(world_idx, dtype=np.int64), (n,)).copy()
-        pos = self.original_world_pos[None] + offsets[world_idx]
-        if self.world_random_scale is not None:
-            s = np.asarray(self.world_random_scale, dtype=np.float64)
-            for e in range(n):
-                rng = np.random.Generator(np.random.Philox(key=self.seed, counter=[self.env_offset + e, 0, 0, 0]))
-                pos[e] += rng.uniform(low=-1.0 * s, high=s, size=3)
+        pos = world_placements(self.seed, self.env_offset + np.arange(n), world_idx, self.world_offsets,
+                               self.world_random_scale, self.original_world_pos)
         return world_idx, pos
+
+    def world_table(self, indices, world_idx_list):
+        """(world_idx, pos) of the episodes / envs with the global `indices`: what a lockstep run
+        gives env i = env_offset + e (world_positions below, with this task's offsets)."""
+        return world_positions(self.seed, indices, world_idx_list, self.world_offsets, self.world_random_scale,
+                               self.original_world_pos)
+
+    def world_slot(self):
+        """Where modify_world puts a world position: (body index, -1) for a body offset,
+        (-1, qpos address) for a free body's joint, (-1, -1) when the task moves nothing."""
+        return self._world_body, -1
 
     def reset(self, seed=None, mask=None):
         """MujocoEnvBase.reset_model (:163-165): qpos = init_qpos, qvel = 0, time = 0, then
@@ -138,6 +169,14 @@ class BatchedMujocoUR5eEnvBase:
         self.reward = self._get_reward()
         self._step_id += 1
         return self._get_obs(), self._get_info()  # _get_reset_info = _get_info (MujocoEnvBase.py:157-158)
+
+    def refresh(self, active=None):
+        """mj_forward of the envs of `active` (u8 [n]; None = all) after their state was rewritten
+        on the device (a recycled slot of the streaming rollout), then the reward; earlier info
+        frames become stale.  What reset() does after writing the state."""
+        self.engine.forward(active=active)
+        self.reward = self._get_reward()
+        self._step_id += 1
 
     def step(self, action, active=None):
         """MujocoEnvBase.step (:82-97): ctrl = action; frame_skip x mj_step; obs; reward.

@@ -77,6 +77,13 @@ class BatchedMujocoUR5ePickEnv(BatchedMujocoUR5eEnvBase):
         self.world_idx = np.zeros(self.num_envs, dtype=np.int64)
         return self.world_idx
 
+    def world_table(self, indices, world_idx_list):
+        n = len(np.asarray(indices).reshape(-1))
+        return np.zeros(n, dtype=np.int64), np.zeros((n, 3))
+
+    def world_slot(self):
+        return -1, -1
+
     def _get_reward(self):
         """MujocoEnvBase._get_reward (:160-161): 0.0."""
         return self.reward.zero_()

@@ -41,6 +41,9 @@ class BatchedMujocoUR5eToolboxEnv(BatchedMujocoUR5eEnvBase):
         self.world_idx = world_idx
         return world_idx
 
+    def world_slot(self):
+        return -1, self._free_qadr
+
     def _get_reward(self):
         """MujocoUR5eToolboxEnv._get_reward (:46-57)."""
         e = self.engine

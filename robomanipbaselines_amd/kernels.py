@@ -87,9 +87,9 @@ class ActEnsembleState:
             self.len.zero_()
             self.head.zero_()
         else:
-            m = mask.bool()
-            self.len[m] = 0
-            self.head[m] = 0
+            m = mask.bool()  # masked fills: no host synchronisation
+            self.len.masked_fill_(m, 0)
+            self.head.masked_fill_(m, 0)
 
     def __call__(self, new_chunk, push=None, active=None):
         act_ensemble(
@@ -330,6 +330,115 @@ def sched_active(sched, n_pre, out=None):
     _chk(out, torch.uint8, (n,), "out")
     N.call("rmbx_sched_active", N.ptr(sched), int(n_pre), N.ptr(out), n, N.stream_ptr())
     return out
+
+
+# ------------------------------------------------------------------------------------------
+# Episode streaming (--num_episodes): phase report, bad-state closure, slot recycle
+# ------------------------------------------------------------------------------------------
+def sched_phases(sched, prev_phase, phase, entered):
+    """phase i32 [n] = each slot's phase index, entered u8 [n] = it changed since the previous call
+    (prev_phase i32 [n], updated in place) (rmbx_sched_phases)."""
+    n = sched.shape[0]
+    _chk(sched, torch.uint8, (n, N.SCHED_DTYPE.itemsize), "sched")
+    _chk(prev_phase, torch.int32, (n,), "prev_phase")
+    _chk(phase, torch.int32, (n,), "phase")
+    _chk(entered, torch.uint8, (n,), "entered")
+    N.call("rmbx_sched_phases", N.ptr(sched), N.ptr(prev_phase), N.ptr(phase), N.ptr(entered), n, N.stream_ptr())
+
+
+def sched_close_bad(sched, time, bad_resets, last_elapsed, n_pre):
+    """Close the episode of every slot the divergence guard rewound (rmbx_sched_close_bad)."""
+    n = sched.shape[0]
+    _chk(sched, torch.uint8, (n, N.SCHED_DTYPE.itemsize), "sched")
+    _chk(time, torch.float64, (n,), "time")
+    _chk(bad_resets, torch.int32, (n,), "bad_resets")
+    _chk(last_elapsed, torch.float64, (n,), "last_elapsed")
+    N.call("rmbx_sched_close_bad", N.ptr(sched), N.ptr(time), N.ptr(bad_resets), N.ptr(last_elapsed), int(n_pre), n,
+           N.stream_ptr())
+
+
+class EpisodeStream:
+    """The device buffers of rmbx_episode_recycle, shape-checked once: the queue (slot_episode,
+    counters, results, world table) this object owns, and the schedule / engine / motion buffers of
+    the caller it re-arms.  `engine` needs the PhysicsEngine tensors (time, qpos, qvel, qacc_ws,
+    _ctrl_store, body_pos, stats and nq / nv / nu / nbody)."""
+
+    def __init__(self, sched, engine, q_cmd, grip_cmd, tgt_R, tgt_p, bad_resets, qpos0, ctrl0, motion0, world_idx,
+                 world_pos, episode_base=0, world_body=-1, world_qadr=-1, final_qpos=False):
+        n, dev = sched.shape[0], sched.device
+        M = len(world_idx)
+        if M < n:
+            raise ValueError(f"{M} episodes for {n} slots: the slots are clamped to the episodes by the caller")
+        nq, nv, nu, nbody = engine.nq, engine.nv, engine.nu, engine.nbody
+        _chk(sched, torch.uint8, (n, N.SCHED_DTYPE.itemsize), "sched")
+        _chk(engine.time, torch.float64, (n,), "time")
+        _chk(engine.qpos, torch.float64, (n, nq), "qpos")
+        _chk(engine.qvel, torch.float64, (n, nv), "qvel")
+        _chk(engine.qacc_ws, torch.float64, (n, nv), "qacc_ws")
+        _chk(engine._ctrl_store, torch.float64, None, "ctrl")
+        if engine._ctrl_store.shape[0] != n or engine._ctrl_store.shape[1] < nu:
+            raise ValueError("ctrl must be [n, >= nu]")
+        _chk(engine.body_pos, torch.float64, (n, nbody, 3), "body_pos")
+        _chk(engine.stats, torch.int32, (n, 4), "stats")
+        _chk(q_cmd, torch.float64, (n, 6), "q_cmd")
+        _chk(grip_cmd, torch.float64, (n, 1), "grip_cmd")
+        _chk(tgt_R, torch.float64, (n, 9), "target_R")
+        _chk(tgt_p, torch.float64, (n, 3), "target_p")
+        _chk(bad_resets, torch.int32, (n,), "bad_resets")
+        if world_body >= nbody or (world_qadr >= 0 and world_qadr + 3 > nq) or (world_body >= 0 and world_qadr >= 0):
+            raise ValueError("world_body / world_qadr out of range (or both given)")
+        f64 = torch.float64
+        self.n, self.M, self.episode_base = n, M, int(episode_base)
+        self.sched, self.engine = sched, engine
+        self.motion = (q_cmd, grip_cmd, tgt_R, tgt_p)
+        self.bad_resets = bad_resets
+        self.qpos0 = torch.tensor(np.asarray(qpos0, np.float64).reshape(nq), dtype=f64, device=dev)
+        self.ctrl0 = torch.tensor(np.asarray(ctrl0, np.float64).reshape(nu), dtype=f64, device=dev)
+        self.motion0 = torch.tensor(np.asarray(motion0, np.float64).reshape(18), dtype=f64, device=dev)
+        self.world_idx = torch.tensor(np.asarray(world_idx, np.int32).reshape(M), dtype=torch.int32, device=dev)
+        self.world_pos = torch.tensor(np.asarray(world_pos, np.float64).reshape(M, 3), dtype=f64, device=dev)
+        self.slot_episode = torch.arange(self.episode_base, self.episode_base + n, dtype=torch.int32, device=dev)
+        self.recycled = torch.zeros(n, dtype=torch.uint8, device=dev)
+        self.counters = torch.tensor([n, 0], dtype=torch.int32, device=dev)  # {next local episode, finished}
+        self.results = torch.zeros((M, N.EPISODE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        self.results.view(torch.int32)[:, 0] = -1  # episode = -1: not recorded yet
+        self.final_qpos = torch.zeros((M, nq), dtype=f64, device=dev) if final_qpos else None
+        self.last_elapsed = torch.zeros(n, dtype=f64, device=dev)
+        self.prev_phase = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        self.phase = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.entered = torch.zeros(n, dtype=torch.uint8, device=dev)
+        b = N.StreamBuffers()
+        for name, t in (("sched", sched), ("slot_episode", self.slot_episode), ("recycled", self.recycled),
+                        ("counters", self.counters), ("results", self.results), ("final_qpos", self.final_qpos),
+                        ("world_idx", self.world_idx), ("world_pos", self.world_pos), ("time", engine.time),
+                        ("qpos", engine.qpos), ("qvel", engine.qvel), ("qacc_ws", engine.qacc_ws),
+                        ("ctrl", engine._ctrl_store), ("body_pos", engine.body_pos), ("stats", engine.stats),
+                        ("qpos0", self.qpos0), ("ctrl0", self.ctrl0), ("q_cmd", q_cmd), ("grip_cmd", grip_cmd),
+                        ("target_R", tgt_R), ("target_p", tgt_p), ("motion0", self.motion0),
+                        ("bad_resets", bad_resets), ("last_elapsed", self.last_elapsed)):
+            setattr(b, name, N.ptr(t))
+        b.n_env, b.n_episodes, b.episode_base = n, M, self.episode_base
+        b.nq, b.nv, b.nu, b.ctrl_stride, b.nbody = nq, nv, nu, engine._ctrl_store.shape[1], nbody
+        b.world_body, b.world_qadr = int(world_body), int(world_qadr)
+        self._bufs = b
+
+    def recycle(self):
+        """Record, re-assign and re-arm every finished slot (rmbx_episode_recycle); the mask of the
+        re-armed slots is self.recycled."""
+        import ctypes
+
+        N.call("rmbx_episode_recycle", ctypes.byref(self._bufs), N.stream_ptr())
+        return self.recycled
+
+    def phases(self):
+        sched_phases(self.sched, self.prev_phase, self.phase, self.entered)
+
+    def close_bad(self, n_pre):
+        sched_close_bad(self.sched, self.engine.time, self.bad_resets, self.last_elapsed, n_pre)
+
+    def records(self):
+        """Host structured array (N.EPISODE_DTYPE) of the recorded episodes, in queue order."""
+        return self.results.cpu().numpy().view(N.EPISODE_DTYPE).reshape(-1)
 
 
 # ------------------------------------------------------------------------------------------

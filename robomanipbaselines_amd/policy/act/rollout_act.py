@@ -65,6 +65,13 @@ class RolloutAct(BatchedRolloutBase):
             self.policy.fuse_transformer()
             enable_gemm_tuning()
 
+    @property
+    def infer_period_calls(self):
+        return self.chunk_size if self.args.no_temp_ensem else 1
+
+    def reset_policy_state(self, mask):
+        self.ens.reset(mask)
+
     def reset_variables(self):
         self.ens = K.ActEnsembleState(self.n, self.chunk_size, self.action_dim, self.model_meta_info["action"],
                                       self.device, temporal_ensemble=not self.args.no_temp_ensem)

@@ -65,19 +65,30 @@ class RolloutDiffusionPolicy(BatchedRolloutBase):
         self.policy = self.policy.eval().requires_grad_(False).to(device=self.device, dtype=self.policy_dtype)
         self.policy.obs_nets = self.policy.obs_nets.to(memory_format=torch.channels_last)
 
+    @property
+    def infer_period_calls(self):
+        return self.n_action_steps
+
+    def reset_policy_state(self, mask):
+        """The sampler draws its noise per call for all rows, so a streaming run's episodes are
+        reproducible for a fixed slot count, not across slot counts."""
+        self.ens.reset(mask)
+        self._reset_obs_history(mask)
+
     def reset_variables(self):
         self.ens = K.ActEnsembleState(self.n, self.n_action_steps, self.action_dim, self.model_meta_info["action"],
                                       self.device, temporal_ensemble=False)
         self.state_buf = None
         self.images_buf = None
         self._calls = 0
+        self._first_obs = None
 
     def get_state(self):
         s = super().get_state()
         if self.state_buf is None:
             self.state_buf = s[:, None].repeat(1, self.n_obs_steps, 1)
         else:
-            self.state_buf = torch.cat([self.state_buf[:, 1:], s[:, None]], dim=1)
+            self.state_buf = self._fill_first_obs(torch.cat([self.state_buf[:, 1:], s[:, None]], dim=1), s, 1)
         return self.state_buf
 
     def get_images(self, dtype):
@@ -94,7 +105,8 @@ class RolloutDiffusionPolicy(BatchedRolloutBase):
         if self.images_buf is None:
             self.images_buf = img[:, :, None].repeat(1, 1, self.n_obs_steps, 1, 1, 1)
         else:
-            self.images_buf = torch.cat([self.images_buf[:, :, 1:], img[:, :, None]], dim=2)
+            self.images_buf = self._fill_first_obs(torch.cat([self.images_buf[:, :, 1:], img[:, :, None]], dim=2),
+                                                   img, 2)
         return self.images_buf
 
     @torch.no_grad()
@@ -105,6 +117,7 @@ class RolloutDiffusionPolicy(BatchedRolloutBase):
             state = self.get_state()
             images = self.get_images(self.policy_dtype)
             chunk = self.policy.predict_action(state, images, use_graph=not self.args.no_graph).float().contiguous()
+            self._first_obs = None
         p = torch.full((self.n,), int(push), dtype=torch.uint8, device=self.device)
         self.policy_action = self.ens(chunk, push=p)
         self._calls += 1

@@ -75,7 +75,8 @@ class RolloutDiffusionPolicy3d(RolloutDiffusionPolicy):
         if self.pointcloud_buf is None:
             self.pointcloud_buf = pc[:, None].repeat(1, self.n_obs_steps, 1, 1)
         else:
-            self.pointcloud_buf = torch.cat([self.pointcloud_buf[:, 1:], pc[:, None]], dim=1)
+            self.pointcloud_buf = self._fill_first_obs(torch.cat([self.pointcloud_buf[:, 1:], pc[:, None]], dim=1),
+                                                       pc, 1)
         return self.pointcloud_buf
 
     @torch.no_grad()
@@ -86,6 +87,7 @@ class RolloutDiffusionPolicy3d(RolloutDiffusionPolicy):
             state = self.get_state()
             pc = self.get_pointcloud()
             chunk = self.policy.predict_action(state, pc, use_graph=not self.args.no_graph).float().contiguous()
+            self._first_obs = None
         p = torch.full((self.n,), int(push), dtype=torch.uint8, device=self.device)
         self.policy_action = self.ens(chunk, push=p)
         self._calls += 1

@@ -106,9 +106,12 @@ class RolloutSarnn(BatchedRolloutBase):
     def reset_lstm_state(self, mask):
         """lstm_state = None for the envs of `mask` (bool / u8 [n]) alone: their (h, c) rows are
         zeroed and their action buffer emptied, every other env's are untouched."""
-        m = mask.to(device=self.device).bool()
-        self.h[m] = 0.0
-        self.c[m] = 0.0
+        self.reset_policy_state(mask.to(device=self.device))
+
+    def reset_policy_state(self, mask):
+        m = mask.bool()  # masked fills: no host synchronisation
+        self.h.masked_fill_(m[:, None], 0.0)
+        self.c.masked_fill_(m[:, None], 0.0)
         self.ens.reset(m)
 
     def get_images(self, dtype=torch.float32):
