@@ -470,6 +470,35 @@ typedef struct rmbx_scene_tables {
   const int32_t* tex_level_adr; /* [ntex][RMBX_TEX_LEVELS]: first texel of each mip level */
   int32_t ntex;
   float sky_rgb[6];
+  /* Shadows (optional; shadows = 0, what a zeroed tail gives: none, every pixel as before).  Hard
+   * shadows of the scene's directional light, one rule for the kernel and its tests:
+   *  - receiver: a pixel's nearest surface (primitive or mesh triangle) whose viewer-facing unit
+   *    normal n has n . L > 0 (the shading's own ndl > 0); other pixels are untouched;
+   *  - shadow ray: origin O = P + 1e-3 L (P the hit point), direction L, the unit vector towards the
+   *    light: light_dir, in the world frame.  Only (0, 0, 1), the direction the shading's 0.3 max(0,
+   *    n.z) term assumes, is accepted (RMBX_ERR_ARG otherwise);
+   *  - occluded iff the ray meets any drawn surface under the camera rays' own rules: every entry of
+   *    the primitive table (the bounding boxes of missing mesh files included; ray parameter > 1e-4,
+   *    an origin inside a primitive sees none of it) and every triangle of mesh_tri (parameter >
+   *    1e-4, one-sided: the winding normal e1 x e2 points towards O).  Geoms that are not drawn cast
+   *    nothing; transparency is ignored, as it is for colour;
+   *  - an occluded receiver loses the light's two terms: 0.3 max(0, n.z) and the Blinn-Phong
+   *    specular term.  Ambient, headlight, emission, texture and the clamp are unchanged; depth and
+   *    hit_geom never change; every colour output (rgb and the policy forms) carries the shadow.
+   * The triangles are rigid in their body frames, so each mesh slot has one static bounding volume
+   * hierarchy over its triangles there, shared by all envs, laid out for a stackless any-hit walk:
+   * bvh_nodes f32 [nnode][8] (16-byte aligned) = (box min xyz, skip link, box max xyz, leaf word),
+   * both words int32 bits; nodes in depth-first order, an inner node's (leaf word 0) first child is
+   * the next node, a leaf's word is (first entry of bvh_tri << 3) | its 1..4 triangles; the skip link
+   * is the node to visit after a miss or a finished leaf (-1: the walk ends); bvh_tri i32 the
+   * triangle indices (into mesh_tri, which keeps its order) of the leaves; bvh_root i32 [nmesh] each
+   * slot's root node (-1: none).  The boxes must contain their triangles (mjcf/bvh.py pads them).
+   * A shadowed rmbx_render_scene_cached ignores the cache (a moving body can shadow a static pixel). */
+  const float* bvh_nodes;
+  const int32_t* bvh_tri;
+  const int32_t* bvh_root;
+  float light_dir[3];
+  int32_t shadows;
 } rmbx_scene_tables;
 #define RMBX_TEX_LEVELS 16 /* mip levels per texture (images up to 32768 texels wide) */
 

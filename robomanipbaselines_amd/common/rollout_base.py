@@ -103,6 +103,10 @@ class BatchedRolloutBase:
         parser.add_argument("--result_filename", type=str, default=None)
         parser.add_argument("--save_last_image", action="store_true")
         parser.add_argument("--output_image_dir", type=str, default=".")
+        parser.add_argument("--shadows", choices=["off", "scene"], default="off",
+                            help="scene: the camera images carry the hard shadows of the scene's light where its "
+                                 "<light> casts them (the Cable, Ring and Pick scenes), as the reference's renders "
+                                 "do; off (default): no shadows")
         # batching (this engine)
         parser.add_argument("--num_envs", type=int, default=None,
                             help="environments stepped in lockstep (default: one per --world_idx_list entry, "

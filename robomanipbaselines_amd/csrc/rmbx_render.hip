@@ -22,7 +22,8 @@
 // flat-shaded triangles; the gradient skybox behind (include/rmbx.h rmbx_scene_tables).  Outputs are
 // written once per pixel: u8 HWC RGB, f32 linear depth, the hit geom id, and/or the policy input
 // tensor (CHW, ImageNet-normalised, bf16 or f32, or the space-to-depth forms) fused so the policy
-// never re-reads the u8 image.
+// never re-reads the u8 image.  Opt-in (rmbx_scene_tables.shadows): hard shadows of the directional
+// light, an any-hit query per lit receiver against the primitives and the meshes' static BVHs.
 
 #include <hip/hip_bf16.h>
 
@@ -246,6 +247,13 @@ struct RenderArgs {
   const uint8_t* prim_static;
   uint2* cache;
   const uint8_t* dirty;
+  // hard shadows of the scene light (the SH instantiations only; include/rmbx.h rmbx_scene_tables):
+  // the mesh slots' stackless BVHs -- node n = bvh_nodes[2 n] (box min, miss / skip link) and
+  // bvh_nodes[2 n + 1] (box max, leaf word: (first entry of bvh_tri << 3) | triangles, 0 = inner node,
+  // whose first child is n + 1); bvh_root [nmesh] each slot's root (-1: none)
+  const float4* bvh_nodes;
+  const int32_t* bvh_tri;
+  const int32_t* bvh_root;
 };
 
 // one texel (RGBA8 word, R in the low byte) as floats in [0, 1]
@@ -672,6 +680,131 @@ __global__ void __launch_bounds__(RASTER_THREADS) raster_kernel(RenderArgs a, in
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Hard shadows of the directional light (include/rmbx.h rmbx_scene_tables, "Shadows"): an any-hit
+// query of the ray O + t D (camera frame, D unit) against every drawn surface under the primary
+// rays' rules -- the block's primitives in LDS (all of them: an occluder can lie outside the tile's
+// frustum) behind a point-to-line reject on their bounding radius, then the mesh slots whose
+// bounding sphere the ray meets, each through its BVH in the body frame.  The BVH is walked without
+// a stack: nodes in depth-first order, a miss (or a finished leaf) follows the node's skip link.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool shadow_tri(const float4* tp, const float* o, const float* d) {
+#pragma clang fp contract(off)
+  const float4 A = tp[0], B = tp[1], C = tp[2];
+  const float v0[3] = {A.x, A.y, A.z}, e1[3] = {A.w, B.x, B.y}, e2[3] = {B.z, B.w, C.x};
+  const float s[3] = {o[0] - v0[0], o[1] - v0[1], o[2] - v0[2]};
+  // one-sided, as the visibility pass: the winding normal must point towards the ray's origin
+  const float nw[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+  if (!(nw[0] * s[0] + nw[1] * s[1] + nw[2] * s[2] > 0.f)) return false;
+  const float p[3] = {d[1] * e2[2] - d[2] * e2[1], d[2] * e2[0] - d[0] * e2[2], d[0] * e2[1] - d[1] * e2[0]};
+  const float det = e1[0] * p[0] + e1[1] * p[1] + e1[2] * p[2];
+  if (fabsf(det) < 1e-30f) return false;
+  const float id = 1.0f / det;
+  const float uu = (s[0] * p[0] + s[1] * p[1] + s[2] * p[2]) * id;
+  if (uu < 0.f || uu > 1.f) return false;
+  const float qv[3] = {s[1] * e1[2] - s[2] * e1[1], s[2] * e1[0] - s[0] * e1[2], s[0] * e1[1] - s[1] * e1[0]};
+  const float vv = (d[0] * qv[0] + d[1] * qv[1] + d[2] * qv[2]) * id;
+  if (vv < 0.f || uu + vv > 1.f) return false;
+  const float t = (e2[0] * qv[0] + e2[1] * qv[1] + e2[2] * qv[2]) * id;
+  return t > 1e-4f;
+}
+
+// does the ray (o, d; the slot's body frame) hit any triangle of the BVH rooted at node n?
+__device__ bool shadow_bvh(const float4* bvh_nodes, const int32_t* bvh_tri, const float* mesh_tri, int n, const float* o,
+                           const float* d) {
+#pragma clang fp contract(off)
+  float inv[3];
+  for (int i = 0; i < 3; i++) inv[i] = 1.0f / (fabsf(d[i]) < 1e-20f ? copysignf(1e-20f, d[i]) : d[i]);
+  while (n >= 0) {
+    const float4 lo = __ldg(bvh_nodes + 2 * (size_t)n), hi = __ldg(bvh_nodes + 2 * (size_t)n + 1);
+    // slab test over t >= 0 (the boxes are padded by the builder; a hair of slack on the interval)
+    const float l[3] = {lo.x, lo.y, lo.z}, h[3] = {hi.x, hi.y, hi.z};
+    float t0 = 0.f, t1 = 1e30f;
+    for (int i = 0; i < 3; i++) {
+      const float ta = (l[i] - o[i]) * inv[i], tb = (h[i] - o[i]) * inv[i];
+      t0 = fmaxf(t0, fminf(ta, tb));
+      t1 = fminf(t1, fmaxf(ta, tb));
+    }
+    const int skip = __float_as_int(lo.w), leaf = __float_as_int(hi.w);
+    if (!(t0 <= t1 * (1.0f + 1e-5f) + 1e-6f)) {
+      n = skip;
+    } else if (leaf == 0) {
+      n = n + 1;
+    } else {
+      const int first = leaf >> 3, cnt = leaf & 7;
+      for (int k = 0; k < cnt; k++) {
+        const int j = __ldg(bvh_tri + first + k);
+        if (shadow_tri(reinterpret_cast<const float4*>(mesh_tri) + 4 * (size_t)j, o, d)) return true;
+      }
+      n = skip;
+    }
+  }
+  return false;
+}
+
+// The light is directional, so D is one vector per block and the bounding-sphere reject is split: per
+// block and item (primitive / mesh slot) the centre's part across D and its bounding radius (sP / mC:
+// xyz, r; r < 0: unbounded, always tested) and its coordinate along D (sPd / mCd); per pixel the
+// origin's part across D (Op) and along it (od).  The reject is then a difference, a dot product and
+// two compares on one 16-byte LDS read; the centre-to-origin vector of a survivor is rebuilt from them.
+// Not inlined: the kernel around the call is then the code of the instantiation without shadows, so
+// depth and hit_geom stay bit-identical to its (inlined, the primary rays' arithmetic was contracted
+// differently).  The LDS tables keep their address space through the call (no flat loads).
+typedef const __attribute__((address_space(3))) float lds_cf;
+template <bool VIS>
+__device__ __attribute__((noinline)) bool shadow_occluded(const float4* bvh_nodes, const int32_t* bvh_tri,
+                                                          const int32_t* bvh_root, const float* mesh_tri, int nmesh,
+                                                          const PrimCam* prims, int np, lds_cf* sP, lds_cf* sPd,
+                                                          const float (*mR)[9], lds_cf* mC, lds_cf* mCd,
+                                                          const float* O, const float* D) {
+#pragma clang fp contract(off)
+  const float od = O[0] * D[0] + O[1] * D[1] + O[2] * D[2];
+  const float Op[3] = {O[0] - od * D[0], O[1] - od * D[1], O[2] - od * D[2]};
+  for (int p = 0; p < np; p++) {
+    const float4 s = make_float4(sP[4 * p], sP[4 * p + 1], sP[4 * p + 2], sP[4 * p + 3]);
+    const float pr = sPd[p] - od;  // the centre's parameter along the ray
+    const float e[3] = {Op[0] - s.x, Op[1] - s.y, Op[2] - s.z};
+    // the primitive's bounding sphere (a hair wider) against the ray: behind it, or off its line
+    if (s.w >= 0.f && (pr < -s.w || e[0] * e[0] + e[1] * e[1] + e[2] * e[2] > s.w * s.w)) continue;
+    const PrimCam& P = prims[p];
+    const float w[3] = {e[0] - pr * D[0], e[1] - pr * D[1], e[2] - pr * D[2]};  // O - c
+    float o_l[3], d_l[3], t, nl[3];
+    for (int i = 0; i < 3; i++) {
+      o_l[i] = P.R[i] * w[0] + P.R[3 + i] * w[1] + P.R[6 + i] * w[2];
+      d_l[i] = P.R[i] * D[0] + P.R[3 + i] * D[1] + P.R[6 + i] * D[2];
+    }
+    bool h = false;
+    switch (P.type) {
+      case RMBX_GEOM_PLANE: h = hit_plane(o_l, d_l, &t, nl); break;
+      case RMBX_GEOM_SPHERE: h = hit_sphere(o_l, d_l, P.s[0], &t, nl); break;
+      case RMBX_GEOM_CAPSULE: h = hit_capsule(o_l, d_l, P.s[0], P.s[1], &t, nl); break;
+      case RMBX_GEOM_CYLINDER: h = hit_cylinder(o_l, d_l, P.s[0], P.s[1], true, &t, nl); break;
+      case RMBX_GEOM_BOX: h = hit_box(o_l, d_l, P.s, &t, nl); break;
+      default: break;
+    }
+    if (h) return true;
+  }
+  if constexpr (VIS) {
+    for (int k = 0; k < nmesh; k++) {
+      const float4 s = make_float4(mC[4 * k], mC[4 * k + 1], mC[4 * k + 2], mC[4 * k + 3]);
+      const float pr = mCd[k] - od;
+      const float e[3] = {Op[0] - s.x, Op[1] - s.y, Op[2] - s.z};
+      if (pr < -s.w || e[0] * e[0] + e[1] * e[1] + e[2] * e[2] > s.w * s.w) continue;
+      const int root = bvh_root[k];
+      if (root < 0) continue;
+      const float w[3] = {e[0] - pr * D[0], e[1] - pr * D[1], e[2] - pr * D[2]};
+      // into the body frame: local = R^T (x - c), R = mR[k] row-major
+      float o_b[3], d_b[3];
+      for (int i = 0; i < 3; i++) {
+        o_b[i] = mR[k][i] * w[0] + mR[k][3 + i] * w[1] + mR[k][6 + i] * w[2];
+        d_b[i] = mR[k][i] * D[0] + mR[k][3 + i] * D[1] + mR[k][6 + i] * D[2];
+      }
+      if (shadow_bvh(bvh_nodes, bvh_tri, mesh_tri, root, o_b, d_b)) return true;
+    }
+  }
+  return false;
+}
+
 // RMBX_RENDER_MINW: minimum waves per SIMD the register allocation targets: 8 (default; 64
 // registers, 136 B/lane of spilled set-up values, none in the ray loop's hot path) -- per
 // 1024-env 8-bit frame 5.74-5.79 ms vs 6.46 at 5 waves (94 registers, no spills), 6.06 at 6,
@@ -684,8 +817,14 @@ __global__ void __launch_bounds__(RASTER_THREADS) raster_kernel(RenderArgs a, in
 // CM: 0 = no cache (every primitive in one pass), 1 = the envs whose cache is valid, 2 = the envs
 // whose cache is rebuilt this call (rmbx_render_scene_cached launches 1 and 2 over all envs; each
 // block of the other kind returns at once)
-template <bool VIS, int CM>
-__global__ void __launch_bounds__(256, RMBX_RENDER_MINW) render_kernel(RenderArgs a) {
+// SH: the shadow query after each lit receiver's ray loop (CM 0 only: a shadowed render bypasses the
+// cache).  It does not fit the 64-register budget above, so it is a compile-time parameter with
+// launch bounds of its own, and the SH = false instantiations are the ones they always were
+#ifndef RMBX_RENDER_SH_MINW
+#define RMBX_RENDER_SH_MINW 4
+#endif
+template <bool VIS, int CM, bool SH = false>
+__global__ void __launch_bounds__(256, SH ? RMBX_RENDER_SH_MINW : RMBX_RENDER_MINW) render_kernel(RenderArgs a) {
   __shared__ PrimCam prims[MAX_PRIM];
   __shared__ int order[MAX_PRIM];        // the block's primitives sorted front to back, once
   __shared__ int tile_sorted[MAX_PRIM];  // the tile's survivors in that order
@@ -693,6 +832,10 @@ __global__ void __launch_bounds__(256, RMBX_RENDER_MINW) render_kernel(RenderArg
   __shared__ CamFrame cf;
   __shared__ float mR[VIS ? MAX_MESH : 1][9];  // mesh slots' body rotations in the camera frame
   __shared__ uint8_t pstat[MAX_PRIM];          // cached modes: 1 for a static primitive
+  // shadows: the bounding spheres of the mesh slots and the primitives, split across / along the
+  // light's direction (shadow_occluded)
+  __shared__ __attribute__((aligned(16))) float mC[VIS && SH ? MAX_MESH : 1][4], sP[SH ? MAX_PRIM : 1][4];
+  __shared__ float mCd[VIS && SH ? MAX_MESH : 1], sPd[SH ? MAX_PRIM : 1];
   const int ntiles = a.tiles_x * a.tiles_y;
   const int env = blockIdx.x / a.groups;
   const int grp = blockIdx.x % a.groups;
@@ -715,6 +858,11 @@ __global__ void __launch_bounds__(256, RMBX_RENDER_MINW) render_kernel(RenderArg
     if (tid < a.nmesh) {
       float c[3];
       mesh_frame(a, env, tid, cf, mR[tid], c);
+      if constexpr (SH) {
+        mC[tid][0] = c[0];
+        mC[tid][1] = c[1];
+        mC[tid][2] = c[2];
+      }
     }
   }
   // the env's primitives in the camera frame, once per block (the block then renders a range
@@ -819,6 +967,25 @@ __global__ void __launch_bounds__(256, RMBX_RENDER_MINW) render_kernel(RenderArg
     pstat[p] = mode ? a.prim_static[p] : 0;
   }
   __syncthreads();
+  if constexpr (SH) {
+    // the shadow query's bounding spheres, from the staged values (a pass of its own: the staging
+    // above stays the code of the instantiations without shadows, so the primary rays' arithmetic and
+    // with it depth and hit_geom are bit-identical to theirs); read after the tile loop's barrier
+    for (int p = tid; p < np; p += blockDim.x) {
+      const PrimCam& P = prims[p];
+      const float cd = P.c[0] * cf.R[6] + P.c[1] * cf.R[7] + P.c[2] * cf.R[8];
+      for (int i = 0; i < 3; i++) sP[p][i] = P.c[i] - cd * cf.R[6 + i];
+      sP[p][3] = P.type != RMBX_GEOM_PLANE && P.rad > 0.f ? P.rad + 1e-4f : -1.f;
+      sPd[p] = cd;
+    }
+    if (VIS && tid < a.nmesh) {
+      const float c[3] = {mC[tid][0], mC[tid][1], mC[tid][2]};
+      const float cd = c[0] * cf.R[6] + c[1] * cf.R[7] + c[2] * cf.R[8];
+      for (int i = 0; i < 3; i++) mC[tid][i] = c[i] - cd * cf.R[6 + i];
+      mC[tid][3] = a.mesh_rad[tid] * (1.0f + 1e-5f) + 1e-4f;
+      mCd[tid] = cd;
+    }
+  }
   // order the primitives front to back by the depth bound (ties by index) once per block: a tile
   // keeps this order for its survivors, and a ray stops at the first primitive whose bound lies
   // behind its nearest hit so far
@@ -1028,6 +1195,15 @@ __global__ void __launch_bounds__(256, RMBX_RENDER_MINW) render_kernel(RenderArg
     const float L[3] = {cf.R[6], cf.R[7], cf.R[8]};
     float ndl = bn[0] * L[0] + bn[1] * L[1] + bn[2] * L[2];
     ndl = ndl > 0 ? ndl : 0;
+    if constexpr (SH) {
+      // a receiver the light does not reach loses the light's two terms (0.3 ndl below and sp)
+      if (ndl > 0.f) {
+        const float O[3] = {best * d[0] + 1e-3f * L[0], best * d[1] + 1e-3f * L[1], best * d[2] + 1e-3f * L[2]};
+        if (shadow_occluded<VIS>(a.bvh_nodes, a.bvh_tri, a.bvh_root, a.mesh_tri, a.nmesh, prims, np, (lds_cf*)&sP[0][0],
+                                 (lds_cf*)sPd, mR, (lds_cf*)&mC[0][0], (lds_cf*)mCd, O, L))
+          ndl = 0.f;
+      }
+    }
     const float shade = 0.1f + 0.6f * ndv + 0.3f * ndl;
     if (a.geom_matinfo) {
       const float* mi = a.geom_matinfo + 6 * bgeom;
@@ -1220,8 +1396,20 @@ extern "C" int rmbx_render_scene_cached(const rmbx_camera* cam, const rmbx_scene
   a.prim_static = nullptr;
   a.cache = nullptr;
   a.dirty = nullptr;
+  // shadows: only the light direction the shading assumes (world +z towards the light); the mesh
+  // slots' BVHs are needed when there are meshes
+  const bool shadows = scene->shadows != 0;
+  RMBX_CHECK_ARG(!shadows || (scene->light_dir[0] == 0.f && scene->light_dir[1] == 0.f && scene->light_dir[2] == 1.f),
+                 "shadows: light_dir must be (0, 0, 1), the direction the shading assumes");
+  RMBX_CHECK_ARG(!shadows || !meshes || (scene->bvh_nodes && scene->bvh_tri && scene->bvh_root &&
+                                         ((uintptr_t)scene->bvh_nodes & 15) == 0),
+                 "shadows: meshes need bvh_nodes (16-byte aligned) / bvh_tri / bvh_root");
+  a.bvh_nodes = reinterpret_cast<const float4*>(scene->bvh_nodes);
+  a.bvh_tri = scene->bvh_tri;
+  a.bvh_root = scene->bvh_root;
   const char* cache_env = std::getenv("RMBX_RENDER_CACHE");  // 0: render every pixel in full (A/B)
-  const bool use_cache = cache && cache->nstatic > 0 && !(cache_env && std::atoi(cache_env) == 0);
+  // (a shadowed render bypasses the cache: a moving body can shadow a cached static pixel)
+  const bool use_cache = cache && cache->nstatic > 0 && !shadows && !(cache_env && std::atoi(cache_env) == 0);
   if (use_cache) {
     RMBX_CHECK_ARG(cache->prim_static && cache->static_prims && cache->cache && cache->snap && cache->dirty &&
                        ((uintptr_t)cache->cache & 7) == 0 && cache->nstatic <= scene->nprim,
@@ -1289,6 +1477,8 @@ extern "C" int rmbx_render_scene_cached(const rmbx_camera* cam, const rmbx_scene
       hipLaunchKernelGGL((rmbx::render_kernel<true, 1>), dim3((unsigned)nblocks), dim3(256), 0, st, a);
       RMBX_CHECK_LAUNCH();
       hipLaunchKernelGGL((rmbx::render_kernel<true, 2>), dim3((unsigned)nblocks), dim3(256), 0, st, a);
+    } else if (shadows) {
+      hipLaunchKernelGGL((rmbx::render_kernel<true, 0, true>), dim3((unsigned)nblocks), dim3(256), 0, st, a);
     } else {
       hipLaunchKernelGGL((rmbx::render_kernel<true, 0>), dim3((unsigned)nblocks), dim3(256), 0, st, a);
     }
@@ -1296,6 +1486,8 @@ extern "C" int rmbx_render_scene_cached(const rmbx_camera* cam, const rmbx_scene
     hipLaunchKernelGGL((rmbx::render_kernel<false, 1>), dim3((unsigned)nblocks), dim3(256), 0, st, a);
     RMBX_CHECK_LAUNCH();
     hipLaunchKernelGGL((rmbx::render_kernel<false, 2>), dim3((unsigned)nblocks), dim3(256), 0, st, a);
+  } else if (shadows) {
+    hipLaunchKernelGGL((rmbx::render_kernel<false, 0, true>), dim3((unsigned)nblocks), dim3(256), 0, st, a);
   } else {
     hipLaunchKernelGGL((rmbx::render_kernel<false, 0>), dim3((unsigned)nblocks), dim3(256), 0, st, a);
   }

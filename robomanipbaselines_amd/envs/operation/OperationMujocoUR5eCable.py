@@ -10,7 +10,7 @@ class OperationMujocoUR5eCable:
     def setup_env(self, render_mode=None):
         self.env = BatchedMujocoUR5eCableEnv(
             self.args.num_envs, self.args.device, world_random_scale=self.args.world_random_scale, seed=self.args.seed,
-            env_offset=self.args.env_offset,
+            env_offset=self.args.env_offset, shadows=getattr(self.args, "shadows", "off"),
         )
 
     def get_pre_motion_phases(self):

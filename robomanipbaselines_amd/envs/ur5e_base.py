@@ -20,7 +20,7 @@ from .. import _native as N  # noqa: F401  (fails loudly if librmbx.so is missin
 from .. import kernels as K
 from .. import model as MD
 from ..engine import PhysicsEngine
-from ..render import Renderer
+from ..render import Renderer, scene_casts_shadows
 
 ARM_JOINTS = ["shoulder_pan_joint", "shoulder_lift_joint", "elbow_joint", "wrist_1_joint", "wrist_2_joint", "wrist_3_joint"]
 GRIPPER_JOINTS = ["right_driver_joint", "right_spring_link_joint", "left_driver_joint", "left_spring_link_joint"]
@@ -63,14 +63,20 @@ class BatchedMujocoUR5eEnvBase:
     world_offsets = None  # [n_world, 3] offsets of world_body per world index
 
     def __init__(self, num_envs, device="cuda:0", world_random_scale=None, seed=0, image_size=(480, 640),
-                 model_name=None, env_offset=0):
+                 model_name=None, env_offset=0, shadows="off"):
+        """shadows: "off" (the default) or "scene": the renderer draws the hard shadows of the scene's
+        light where the scene's <light> casts them (castshadow, MuJoCo's default: the Cable, Ring and
+        Pick scenes; the others declare castshadow="false" and render as with "off")."""
+        if shadows not in ("off", "scene"):
+            raise ValueError(f"shadows must be 'off' or 'scene', not {shadows!r}")
         model_name = model_name or self.model_name
         self.num_envs = int(num_envs)
         self.device = torch.device(device)
         self.arrays = MD.load(model_name)
         self.info = MD.ModelInfo(self.arrays)
         self.engine = PhysicsEngine(self.arrays, self.num_envs, device)
-        self.renderer = Renderer(self.arrays, device, width=image_size[1], height=image_size[0])
+        self.shadows = shadows == "scene" and scene_casts_shadows(self.arrays)
+        self.renderer = Renderer(self.arrays, device, width=image_size[1], height=image_size[0], shadows=self.shadows)
         self.world_random_scale = world_random_scale
         self.seed = int(seed)
         # global index of local env 0 (the rank's shard start): noise streams are keyed by the

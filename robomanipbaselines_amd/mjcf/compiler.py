@@ -484,7 +484,7 @@ def compile_mjcf(path, missing_mesh_box=(0.045, 0.0125, 0.0125), convex_meshes=F
 
     # ---- body tree
     bodies = []  # dicts
-    joints, geoms, sites, cams = [], [], [], []
+    joints, geoms, sites, cams, lights = [], [], [], [], []
     mesh_cache = {}
 
     def get_mesh(name):
@@ -562,6 +562,15 @@ def compile_mjcf(path, missing_mesh_box=(0.045, 0.0125, 0.0125), convex_meshes=F
                 a = attrs_of(ch, cc)
                 cams.append(dict(name=a.get("name", ""), body=bid, pos=np.array(_floats(a.get("pos", "0 0 0"))), quat=frame_quat(a),
                                  fovy=float(a.get("fovy", 45.0))))
+            elif ch.tag == "light":
+                # (defaults: mjsLight, [ext] mujoco 3.1.6 -- a light casts shadows unless told not to)
+                a = attrs_of(ch, cc)
+                lights.append(dict(name=a.get("name", ""), body=bid, pos=np.array(_floats(a.get("pos", "0 0 0"))),
+                                   dir=np.array(_floats(a.get("dir", "0 0 -1"))),
+                                   directional=a.get("directional", "false") == "true",
+                                   castshadow=a.get("castshadow", "true") == "true",
+                                   diffuse=np.array(_floats(a.get("diffuse", "0.7 0.7 0.7"))),
+                                   specular=np.array(_floats(a.get("specular", "0.3 0.3 0.3")))))
         for ch in node:
             if ch.tag == "body":
                 add_body(ch, bid, cc)
@@ -751,6 +760,14 @@ def compile_mjcf(path, missing_mesh_box=(0.045, 0.0125, 0.0125), convex_meshes=F
     M.textures, M.material_props, M.skybox = textures, material_props, skybox
     M.sites = sites
     M.cams = cams
+    M.lights = lights
+    # <visual><headlight>: MuJoCo's camera-attached light (defaults of mjVisual.headlight)
+    M.headlight = dict(ambient=np.array([0.1] * 3), diffuse=np.array([0.4] * 3), specular=np.array([0.5] * 3))
+    for v in root.findall("visual"):
+        for hl in v.findall("headlight"):
+            for k in ("ambient", "diffuse", "specular"):
+                if k in hl.attrib:
+                    M.headlight[k] = np.array(_floats(hl.attrib[k]))
 
     # ---- actuators, tendons, equality, sensors, excludes
     tendons = []
@@ -1070,3 +1087,32 @@ def visual_arrays(M):
             "tex_type": np.array(tex_type, np.int32), "tex_size": np.array(tex_size, np.int32).reshape(-1, 2),
             "tex_adr": np.array(tex_adr, np.int32),
             "tex_rgb": np.concatenate(texels) if texels else np.zeros((0, 3), np.uint8), "sky_rgb": sky}
+
+
+def light_arrays(M):
+    """The lights of a compiled model, for the renderer's shadows (csrc/rmbx_render.hip):
+
+    * light_dir f64 [nlight, 3]: the unit direction each light shines along, world frame at qpos0
+    * light_directional, light_castshadow i32 [nlight] (MuJoCo's default: a light casts shadows)
+    * light_diffuse, light_specular f64 [nlight, 3]
+    * headlight_ambient, headlight_diffuse, headlight_specular f64 [3]: <visual><headlight>
+
+    Only lights of the world body are placed (the reference's scenes have no others: a light on
+    another body is refused), and a light that casts shadows must be directional (the renderer's
+    shadow rays are parallel)."""
+    for l in M.lights:
+        if l["body"] != 0:
+            raise ValueError(f"light {l['name']!r} is on body {M.body_name[l['body']]!r}: only lights of the world body are supported")
+        if l["castshadow"] and not l["directional"]:
+            raise ValueError(f"light {l['name']!r} casts shadows but is not directional: only directional lights cast shadows here")
+        if not np.linalg.norm(l["dir"]) > 0:
+            raise ValueError(f"light {l['name']!r} has a zero dir")
+    n = len(M.lights)
+    return {"light_dir": np.array([l["dir"] / np.linalg.norm(l["dir"]) for l in M.lights], np.float64).reshape(n, 3),
+            "light_directional": np.array([l["directional"] for l in M.lights], np.int32),
+            "light_castshadow": np.array([l["castshadow"] for l in M.lights], np.int32),
+            "light_diffuse": np.array([l["diffuse"] for l in M.lights], np.float64).reshape(n, 3),
+            "light_specular": np.array([l["specular"] for l in M.lights], np.float64).reshape(n, 3),
+            "headlight_ambient": np.asarray(M.headlight["ambient"], np.float64),
+            "headlight_diffuse": np.asarray(M.headlight["diffuse"], np.float64),
+            "headlight_specular": np.asarray(M.headlight["specular"], np.float64)}

@@ -223,10 +223,37 @@ def save(arrays, path):
     np.savez_compressed(path, **arrays)
 
 
+def lights_path(path):
+    """The side file of a packed asset that holds its scene lights (mjcf/compiler.light_arrays), for
+    assets packed before the lights were compiled (tools/compile_models.py --lights): a few numbers
+    per scene, kept as text."""
+    return path[:-len(".npz")] + ".lights.json"
+
+
+def save_lights(lights, path):
+    """Write light arrays as JSON: name -> {"dtype", "data"} (nested lists)."""
+    import json
+
+    with open(path, "w") as f:
+        json.dump({k: {"dtype": str(np.asarray(v).dtype), "data": np.asarray(v).tolist()} for k, v in sorted(lights.items())},
+                  f, indent=1)
+        f.write("\n")
+
+
+def load_lights(path):
+    import json
+
+    with open(path) as f:
+        return {k: np.asarray(v["data"], dtype=np.dtype(v["dtype"])) for k, v in json.load(f).items()}
+
+
 def load(name_or_path):
     path = name_or_path if os.path.exists(name_or_path) else os.path.join(ASSET_DIR, name_or_path + ".npz")
     with np.load(path, allow_pickle=False) as f:
-        return _with_defaults({k: f[k] for k in f.files})
+        arrays = {k: f[k] for k in f.files}
+    if "light_dir" not in arrays and path.endswith(".npz") and os.path.exists(lights_path(path)):
+        arrays.update(load_lights(lights_path(path)))
+    return _with_defaults(arrays)
 
 
 def _with_defaults(arrays):

@@ -13,6 +13,7 @@ primitives).
 """
 
 import ctypes
+import os
 
 import numpy as np
 import torch
@@ -101,9 +102,49 @@ def mip_pyramid(img):
     return out
 
 
+# the shading constants of csrc/rmbx_render.hip: MuJoCo's default headlight and the scenes' one light
+AMBIENT, HEADLIGHT_DIFFUSE, LIGHT_DIFFUSE = 0.1, 0.6, 0.3
+
+
+def scene_casts_shadows(arrays):
+    """Does the compiled scene's light cast shadows (`--shadows scene`)?  MuJoCo's default is that a
+    light does; a scene compiled without its light arrays casts none."""
+    if "light_castshadow" not in arrays:
+        return False
+    return bool(np.any(np.asarray(arrays["light_castshadow"]) != 0))
+
+
+def shadow_light(arrays):
+    """The unit vector towards the light whose shadows the renderer draws, world frame.  The shading
+    constants are hard-coded in the kernel, so a scene that carries its light arrays
+    (compiler.light_arrays) is checked against them: ambient 0.1, headlight diffuse 0.6 and specular
+    0, exactly one light, directional, of diffuse 0.3, pointing along world -z -- ValueError
+    otherwise.  A scene without the arrays (a synthetic test scene) has the light the shading assumes."""
+    if "light_dir" not in arrays:
+        return np.array([0.0, 0.0, 1.0])
+
+    def same(name, value):
+        return np.allclose(np.asarray(arrays[name], np.float64), value, rtol=0, atol=1e-9)
+
+    d = np.asarray(arrays["light_dir"], np.float64).reshape(-1, 3)
+    if not (same("headlight_ambient", AMBIENT) and same("headlight_diffuse", HEADLIGHT_DIFFUSE)
+            and same("headlight_specular", 0.0)):
+        raise ValueError("shadows: the scene's headlight is not the one the shading assumes "
+                         f"(ambient {AMBIENT}, diffuse {HEADLIGHT_DIFFUSE}, specular 0)")
+    if len(d) != 1 or not np.all(np.asarray(arrays["light_directional"]) != 0) or not same("light_diffuse", LIGHT_DIFFUSE):
+        raise ValueError(f"shadows: the scene must have exactly one light, directional, of diffuse {LIGHT_DIFFUSE}")
+    L = -d[0] / np.linalg.norm(d[0])
+    if not np.allclose(L, (0.0, 0.0, 1.0), rtol=0, atol=1e-9):
+        raise ValueError(f"shadows: the light must point along world -z (the shading's n.z term); it points along {d[0]}")
+    return np.array([0.0, 0.0, 1.0])
+
+
 class Renderer:
-    def __init__(self, arrays, device, width=640, height=480):
+    def __init__(self, arrays, device, width=640, height=480, shadows=False):
+        """shadows: hard shadows of the scene's directional light (include/rmbx.h rmbx_scene_tables);
+        a shadowed render does not use the static-background cache."""
         self.arrays = arrays
+        self.shadows = bool(shadows)
         pi, pf = build_prims(arrays)
         self.nprim = len(pi)
         self.prim_i32 = torch.tensor(pi, device=device)
@@ -159,12 +200,28 @@ class Renderer:
             sc.ntex = len(desc)
             for i, v in enumerate(np.asarray(arrays["sky_rgb"], np.float64).reshape(-1)):
                 sc.sky_rgb[i] = float(v)
+        if self.shadows:
+            L = shadow_light(arrays)
+            for i in range(3):
+                sc.light_dir[i] = float(L[i])
+            sc.shadows = 1
+            if self.mesh_tri is not None:
+                # one static BVH per mesh slot in its body frame, shared by all envs (mjcf/bvh.py)
+                from .mjcf import bvh
+
+                t = bvh.build(arrays["rmesh_tri"], arrays["rmesh_tri_adr"], arrays["rmesh_tri_num"])
+                self.bvh_nodes = torch.tensor(t["bvh_nodes"], device=device).contiguous()
+                self.bvh_tri = torch.tensor(t["bvh_tri"], device=device)
+                self.bvh_root = torch.tensor(t["bvh_root"], device=device)
+                sc.bvh_nodes, sc.bvh_tri, sc.bvh_root = (self.bvh_nodes.data_ptr(), self.bvh_tri.data_ptr(),
+                                                         self.bvh_root.data_ptr())
         self._scene = sc
         # static-background caches (rmbx_render_scene_cached): the primitives of bodies welded to the
         # world, one cache per world-fixed camera (allocated at its first render)
         if "body_weldid" in arrays and self.nprim:
             weld, gbody = np.asarray(arrays["body_weldid"]), np.asarray(arrays["geom_body"])
-            mocap = set(int(b) for b in np.asarray(arrays["body_mocapid"]).nonzero()[0]) if "body_mocapid" in arrays else set()
+            # (MuJoCo's body_mocapid is -1 for a body that is not a mocap body)
+            mocap = set(int(b) for b in np.nonzero(np.asarray(arrays["body_mocapid"]) >= 0)[0]) if "body_mocapid" in arrays else set()
             stat = np.array([1 if weld[gbody[g]] == 0 and int(gbody[g]) not in mocap else 0 for g in pi[:, 0]], np.uint8)
         else:
             stat = np.zeros(self.nprim, np.uint8)
@@ -195,7 +252,10 @@ class Renderer:
 
     def _cache(self, camera_name, cam, n):
         """The static-background cache of a world-fixed camera (include/rmbx.h rmbx_render_cache), or
-        None (a camera on a moving body, a scene without static primitives)."""
+        None (a camera on a moving body, a scene without static primitives, a shadowed render, or
+        RMBX_RENDER_CACHE=0: the call would ignore it, so its n * H * W * 8 bytes are not allocated)."""
+        if self.shadows or os.environ.get("RMBX_RENDER_CACHE", "").strip() == "0":
+            return None
         nst = int(self.static_prims.numel())
         weld = self.arrays["body_weldid"] if "body_weldid" in self.arrays else None
         if nst == 0 or weld is None or int(np.asarray(weld)[cam.body]) != 0:

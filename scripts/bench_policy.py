@@ -7,7 +7,8 @@ ms per batched infer_policy call.
 * configs[4]: DP3 x1024 on MujocoUR5ePick with the synthetic tactile channel computed every
   env-step (--tactile; the reference's tactile plugin is absent, envs/ur5e_pick.py);
 * Mlp on the cable scene;
-* Sarnn on the cable scene (fp32; RMBX_SARNN_FUSED=0 times the unfused torch route).
+* Sarnn on the cable scene (fp32; RMBX_SARNN_FUSED=0 times the unfused torch route);
+* Act on the cable scene (bench.py's workload through this loop: the A/B of --shadows off / scene).
 
     python scripts/bench_policy.py DiffusionPolicy --num_envs 2048 --steps 24 --warmup 8
     python scripts/bench_policy.py DiffusionPolicy3d --num_envs 1024 --tactile
@@ -33,9 +34,10 @@ from robomanipbaselines_amd.envs.operation.OperationMujocoUR5ePick import Operat
 
 ENVS = {"MujocoUR5eCable": OperationMujocoUR5eCable, "MujocoUR5ePick": OperationMujocoUR5ePick}
 DEFAULT_ENV = {"DiffusionPolicy": "MujocoUR5ePick", "DiffusionPolicy3d": "MujocoUR5ePick", "Mlp": "MujocoUR5eCable",
-               "Sarnn": "MujocoUR5eCable"}
+               "Sarnn": "MujocoUR5eCable", "Act": "MujocoUR5eCable"}
 
 POLICIES = {
+    "Act": ("robomanipbaselines_amd.policy.act.rollout_act", "RolloutAct"),
     "DiffusionPolicy": ("robomanipbaselines_amd.policy.diffusion_policy.rollout_diffusion_policy",
                         "RolloutDiffusionPolicy"),
     "DiffusionPolicy3d": ("robomanipbaselines_amd.policy.diffusion_policy_3d.rollout_diffusion_policy_3d",
@@ -54,6 +56,7 @@ def main():
     p.add_argument("--precision", choices=["bf16", "fp32"], default=None, help="default: bf16 (Sarnn: fp32, its only mode)")
     p.add_argument("--env", choices=sorted(ENVS), default=None, help="default: the BASELINE config's scene")
     p.add_argument("--tactile", action="store_true", help="synthetic tactile every env-step (Pick scene)")
+    p.add_argument("--shadows", choices=["off", "scene"], default="off", help="the renderer's shadows (Rollout.py --shadows)")
     a = p.parse_args()
     a.env = a.env or DEFAULT_ENV[a.policy]
     a.precision = a.precision or ("fp32" if a.policy == "Sarnn" else "bf16")
@@ -66,7 +69,8 @@ def main():
         pass
 
     argv = ["--num_envs", str(a.num_envs), "--device", "cuda:0", "--world_idx_list", *[str(i) for i in range(6)],
-            "--world_random_scale", "0.01", "0.01", "0.0", "--seed", "0", "--precision", a.precision] + (["--tactile"] if a.tactile else [])
+            "--world_random_scale", "0.01", "0.01", "0.0", "--seed", "0", "--precision", a.precision,
+            "--shadows", a.shadows] + (["--tactile"] if a.tactile else [])
     t_start = time.time()
 
     def log(msg):
@@ -113,7 +117,7 @@ def main():
                       "ms_per_step": round(dt * 1e3 / a.steps, 3), "infer_calls": len(inf),
                       "infer_ms_per_call": round(float(np.mean(inf)), 3) if inf else None,
                       "scene": a.env + (" minus YCB_sim" if a.env == "MujocoUR5ePick" else ""),
-                      "tactile": "synthetic, every env-step" if a.tactile else None,
+                      "tactile": "synthetic, every env-step" if a.tactile else None, "shadows": a.shadows,
                       "data": "synthetic (random-init weights)"}), flush=True)
 
 

@@ -61,9 +61,35 @@ def add_visual(name, path):
           os.path.getsize(out), "bytes")
 
 
+def add_lights(name, path):
+    """Add the scene's lights (compiler.light_arrays) to an existing asset as its side file
+    <name>.lights.json, which model.load merges in: the packed asset itself, physics arrays and all,
+    is not rewritten (checked: the geom order must be the compiled one).  A full compile packs the
+    lights into the asset and needs no side file."""
+    import numpy as np
+
+    M = C.compile_mjcf(path, **OPTIONS.get(name, {}))
+    out = os.path.join(MD.ASSET_DIR, name + ".npz")
+    arrays = MD.load(out)
+    names = [str(x) for x in arrays["names_geom"]]
+    if names != [g["name"] for g in M.geoms] or not np.array_equal(arrays["geom_type"], [g["type"] for g in M.geoms]):
+        raise RuntimeError(f"{name}: the asset's geoms are not the compiled model's: recompile the asset")
+    lights = C.light_arrays(M)
+    assert not set(lights) & set(np.load(out).files), "the asset already carries its lights"
+    out = MD.lights_path(out)
+    MD.save_lights(lights, out)
+    print(name, "lights", len(lights["light_dir"]), "castshadow", lights["light_castshadow"].tolist(), "->", out,
+          os.path.getsize(out), "bytes")
+
+
 if __name__ == "__main__":
     os.makedirs(MD.ASSET_DIR, exist_ok=True)
     only = [a for a in sys.argv[1:] if not a.startswith("--")]
+    if "--lights" in sys.argv:
+        for name, path in SCENES.items():
+            if not only or name in only:
+                add_lights(name, path)
+        sys.exit(0)
     if "--visual" in sys.argv:
         for name, path in SCENES.items():
             if not only or name in only:
@@ -79,6 +105,8 @@ if __name__ == "__main__":
         arrays.update(MB.render_meshes(M.geoms, cell=RENDER_MESH_CELL))
         # materials and textures of the renderer
         arrays.update(C.visual_arrays(M))
+        # the scene's lights (the renderer's shadows)
+        arrays.update(C.light_arrays(M))
         out = os.path.join(MD.ASSET_DIR, name + ".npz")
         MD.save(arrays, out)
         print(name, "nq", M.nq, "nv", M.nv, "pairs", len(M.pairs), "->", out, os.path.getsize(out), "bytes")
