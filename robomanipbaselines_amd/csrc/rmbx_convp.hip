@@ -23,10 +23,11 @@
 // (tile, channel block) units; one K step per tap (32 channels), nine per chunk, one barrier each;
 // W of the next step is loaded into registers under this step's MFMAs and stored to the other W
 // buffer after them; the next chunk's patch (a 32-channel chunk of the tile, or the next unit's
-// first) is loaded under the chunk's first taps, its max reduced in LDS mid-chunk, and it is
-// split and stored after the chunk's last MFMAs (one extra barrier per chunk; splitting it in
-// registers during the chunk's last W group instead was slower: the VALU beside the MFMAs costs
-// more than it hides, profiles/r4_conv3x3_patch_presplit_ab.log).
+// first) is loaded under the chunk's first taps, its max reduced mid-chunk (across each wave by
+// DPP, then one LDS atomic per wave), and it is split and stored after the chunk's last MFMAs (one
+// extra barrier per chunk; splitting it in registers during the chunk's last W group instead was
+// slower: the VALU beside the MFMAs costs more than it hides,
+// profiles/r4_conv3x3_patch_presplit_ab.log).
 // LDS images: patch [2 pieces][pixel][4 x 16-B slots of 8 channels], W [2 buffers][2 pieces][BN
 // rows][4 slots]; 16-B slot s of row / pixel r at s ^ ((r >> 1) & 3): the 16-lane groups of every
 // fragment read cover all 64 banks.
@@ -135,6 +136,20 @@ __device__ __forceinline__ void conv3x3p_body(const ConvPArgs& a) {
     for (int i = 0; i < NPR; ++i)
       m = fmaxf(m, fmaxf(fmaxf(fabsf(pr[i].x), fabsf(pr[i].y)), fmaxf(fabsf(pr[i].z), fabsf(pr[i].w))));
     return m;
+  };
+  // the wave's max of a non-negative float, as its bits and wave-uniform: butterflies within each
+  // row of 16 lanes by DPP, then the four rows by readlane.  Handed a per-lane value, hipcc turns
+  // the LDS atomicMax into a loop over the 64 lanes (readlane + s_max, some 450 scalar instructions
+  // per wave and chunk, all eight waves at once ahead of a barrier); handed a uniform one, into one
+  // elected lane's ds_max.
+  auto wave_max_bits = [](float m) {
+    int v = __float_as_int(m);
+    v = max(v, __builtin_amdgcn_mov_dpp(v, 0xB1, 0xf, 0xf, false));   // lane ^ 1
+    v = max(v, __builtin_amdgcn_mov_dpp(v, 0x4E, 0xf, 0xf, false));   // lane ^ 2
+    v = max(v, __builtin_amdgcn_mov_dpp(v, 0x141, 0xf, 0xf, false));  // mirrored within 8 lanes
+    v = max(v, __builtin_amdgcn_mov_dpp(v, 0x140, 0xf, 0xf, false));  // mirrored within 16 lanes
+    return (unsigned int)max(max(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
+                             max(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
   };
   auto store_patch = [&](int t) {
 #pragma unroll
@@ -335,7 +350,7 @@ __device__ __forceinline__ void conv3x3p_body(const ConvPArgs& a) {
   load_patch(u, 0);
   load_w(u, 0, 0);  // group 0
   __syncthreads();
-  atomicMax(&sMax, __float_as_uint(patch_max()));
+  atomicMax(&sMax, wave_max_bits(patch_max()));
   __syncthreads();
   int t_cur = chunk_t(sMax);
   store_patch(t_cur == CP_TNONE ? 0 : t_cur);
@@ -363,7 +378,7 @@ __device__ __forceinline__ void conv3x3p_body(const ConvPArgs& a) {
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int k = 0; k < WG; ++k) mfma_tap(WG * g + k, k, wb);
-      if (g == NG / 2 && more) atomicMax(&sMax, __float_as_uint(patch_max()));
+      if (g == NG / 2 && more) atomicMax(&sMax, wave_max_bits(patch_max()));
       if constexpr ((VAR & 4) == 0) store_w(wb ^ 1);
       __syncthreads();
       wb ^= 1;
