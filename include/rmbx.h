@@ -499,7 +499,29 @@ typedef struct rmbx_scene_tables {
   const int32_t* bvh_root;
   float light_dir[3];
   int32_t shadows;
+  /* Samples (optional; samples = 0 or 1, what a zeroed tail gives: one ray through each pixel centre,
+   * every output as before; 4: four samples per pixel; anything else RMBX_ERR_ARG).  One rule for the
+   * kernel and its tests:
+   *  - sample k of pixel (x, y) is the ray through the continuous pixel coordinate (x + sx_k, y + sy_k),
+   *    (sx, sy) = RMBX_SAMPLE_PATTERN below: the 4x rotated grid, y growing downwards as in the image
+   *    (the pixel centre is (x + 0.5, y + 0.5));
+   *  - each sample is cast and shaded exactly as a pixel-centre ray through that coordinate is: the
+   *    same nearest-hit order, znear clipping of triangles, materials and textures (the level of detail
+   *    from the same one-pixel footprint), skybox and 8-bit rounding (uint8)(c * 255 + 0.5); with
+   *    shadows, each sample casts its own shadow ray from its own hit point under the rule above;
+   *  - resolve: the pixel's colour is (s0 + s1 + s2 + s3 + 2) >> 2 per channel over the four 8-bit
+   *    sample colours; rgb and every policy form derive from that 8-bit pixel as they do from the
+   *    single-sample pixel;
+   *  - depth and hit_geom stay those of the pixel-centre ray, bitwise what samples = 1 gives.
+   * This is supersampling (every sample shaded), not OpenGL's multisampling.
+   * samp: caller-provided device workspace u32 [n_env][H][W] (needed only when samples = 4 and rgb or
+   * policy_img is given), no contract on entry or return: the four sample passes sum the 8-bit colours
+   * in it, 10 bits per channel, R lowest; an inactive env's words are not touched.  vis / tflag are
+   * used, and left empty, by every pass.  A 4-sample rmbx_render_scene_cached ignores the cache. */
+  uint32_t* samp;
+  int32_t samples;
 } rmbx_scene_tables;
+#define RMBX_SAMPLE_PATTERN {{0.375f, 0.125f}, {0.875f, 0.375f}, {0.125f, 0.625f}, {0.625f, 0.875f}}
 #define RMBX_TEX_LEVELS 16 /* mip levels per texture (images up to 32768 texels wide) */
 
 int rmbx_render_scene(const rmbx_camera* cam, const rmbx_scene_tables* scene, const double* gxpos,

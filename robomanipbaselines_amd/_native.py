@@ -142,7 +142,7 @@ class SceneTables(ctypes.Structure):
                 ("tflag", _c_p), ("geom_texid", _c_p), ("geom_matinfo", _c_p), ("tex_rgba", _c_p), ("tex_desc", _c_p),
                 ("tex_level_adr", _c_p), ("ntex", ctypes.c_int32), ("sky_rgb", ctypes.c_float * 6),
                 ("bvh_nodes", _c_p), ("bvh_tri", _c_p), ("bvh_root", _c_p), ("light_dir", ctypes.c_float * 3),
-                ("shadows", ctypes.c_int32)]
+                ("shadows", ctypes.c_int32), ("samp", _c_p), ("samples", ctypes.c_int32)]
 
 
 class RenderCache(ctypes.Structure):

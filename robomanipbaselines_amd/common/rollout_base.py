@@ -107,6 +107,11 @@ class BatchedRolloutBase:
                             help="scene: the camera images carry the hard shadows of the scene's light where its "
                                  "<light> casts them (the Cable, Ring and Pick scenes), as the reference's renders "
                                  "do; off (default): no shadows")
+        parser.add_argument("--offsamples", choices=["1", "4", "scene"], default="1",
+                            help="samples per pixel of the camera images: 4 averages the 4x rotated-grid samples "
+                                 "(anti-aliased edges, as the reference's multisampled offscreen renders); scene: "
+                                 "the scene's <visual><quality offsamples> (MuJoCo's default 4; a value other than "
+                                 "0, 1 or 4 is refused); 1 (default): one ray through each pixel centre")
         # batching (this engine)
         parser.add_argument("--num_envs", type=int, default=None,
                             help="environments stepped in lockstep (default: one per --world_idx_list entry, "

@@ -24,6 +24,9 @@
 // tensor (CHW, ImageNet-normalised, bf16 or f32, or the space-to-depth forms) fused so the policy
 // never re-reads the u8 image.  Opt-in (rmbx_scene_tables.shadows): hard shadows of the directional
 // light, an any-hit query per lit receiver against the primitives and the meshes' static BVHs.
+// Opt-in (rmbx_scene_tables.samples = 4): four samples per pixel -- the two passes once per sample
+// position, the 8-bit colours summed in a workspace, a resolve kernel that averages them into rgb and
+// the policy form; depth and the hit geom from the ordinary pixel-centre passes.
 
 #include <hip/hip_bf16.h>
 
@@ -31,6 +34,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 #include "rmbx_math.h"
 #include "rmbx_model.h"
 
@@ -256,6 +260,30 @@ struct RenderArgs {
   const int32_t* bvh_root;
 };
 
+// 4 samples per pixel (include/rmbx.h rmbx_scene_tables, "Samples"): what the MS instantiations and
+// the resolve take on top (the other instantiations keep the arguments, and the code, they had): the
+// pass's sample position in the pixel (theirs: the centre, the constant 0.5f) and samp [n][H][W], the
+// pixel's 8-bit sample colours summed per channel, 10 bits each (R lowest): stored by the first pass
+// (sfirst), added to by the others, averaged by resolve_kernel
+struct RenderArgsMS : RenderArgs {
+  float sox, soy;
+  uint32_t* samp;
+  int sfirst;
+};
+template <bool MS>
+using RenderArgsOf = std::conditional_t<MS, RenderArgsMS, RenderArgs>;
+// the sample position of a pass: a constant unless MS
+template <bool MS>
+__device__ __forceinline__ float sample_x(const RenderArgsOf<MS>& a) {
+  if constexpr (MS) return a.sox;
+  else return 0.5f;
+}
+template <bool MS>
+__device__ __forceinline__ float sample_y(const RenderArgsOf<MS>& a) {
+  if constexpr (MS) return a.soy;
+  else return 0.5f;
+}
+
 // one texel (RGBA8 word, R in the low byte) as floats in [0, 1]
 __device__ __forceinline__ void texel(const uint32_t* t, int idx, float w, float* c) {
   const uint32_t v = __ldg(t + idx);
@@ -453,7 +481,8 @@ struct TriCam {
 // the triangle in the camera frame, its near-plane-clipped projection (vertices in front of the
 // near plane and the points where edges cross it) in pixel coordinates, the range of pixel centres
 // that projection can cover and its edges
-__device__ __forceinline__ void tri_setup(const RenderArgs& a, const float4* tp, const float* R, const float* c,
+template <bool MS>
+__device__ __forceinline__ void tri_setup(const RenderArgsOf<MS>& a, const float4* tp, const float* R, const float* c,
                                           float tanh_, float aspect, TriCam& T) {
   // no FMA contraction here and in tri_cover: a triangle's depths must be bit-identical whichever
   // path covered it (its own lane or its wave) and however the compiler inlined it
@@ -513,12 +542,13 @@ __device__ __forceinline__ void tri_setup(const RenderArgs& a, const float4* tp,
   }
   float xl = fminf(fminf(X[0], X[1]), fminf(X[2], X[3])), xh = fmaxf(fmaxf(X[0], X[1]), fmaxf(X[2], X[3]));
   float yl = fminf(fminf(Y[0], Y[1]), fminf(Y[2], Y[3])), yh = fmaxf(fmaxf(Y[0], Y[1]), fmaxf(Y[2], Y[3]));
-  // pixel-centre ranges a hair wider than the projection
+  // pixel-centre ranges a hair wider than the projection (MS: the ranges of the pass's sample)
   const float eps = 1e-3f;
-  T.x0 = max((int)ceilf(fmaxf(xl - 0.5f - eps, -1.f)), 0);
-  T.x1 = min((int)floorf(fminf(xh - 0.5f + eps, (float)W)), W - 1);
-  T.y0 = max((int)ceilf(fmaxf(yl - 0.5f - eps, -1.f)), 0);
-  T.y1 = min((int)floorf(fminf(yh - 0.5f + eps, (float)H)), H - 1);
+  const float ox = sample_x<MS>(a), oy = sample_y<MS>(a);
+  T.x0 = max((int)ceilf(fmaxf(xl - ox - eps, -1.f)), 0);
+  T.x1 = min((int)floorf(fminf(xh - ox + eps, (float)W)), W - 1);
+  T.y0 = max((int)ceilf(fmaxf(yl - oy - eps, -1.f)), 0);
+  T.y1 = min((int)floorf(fminf(yh - oy + eps, (float)H)), H - 1);
   // edges: inside is where every unit-normal edge function is >= -tol, oriented by the polygon's
   // signed area; tol = 0.02 px plus the rounding of the edge function at this coordinate magnitude
   float area2 = 0.f;
@@ -545,14 +575,17 @@ __device__ __forceinline__ void tri_setup(const RenderArgs& a, const float4* tp,
   }
 }
 
-// one pixel centre: its camera ray (origin 0) against the triangle (Moller-Trumbore); the nearest
-// hit per pixel is kept by an atomic min of (depth bits << 32 | triangle index)
-__device__ __forceinline__ void tri_cover(const RenderArgs& a, const TriCam& T, unsigned j, int px, int py,
+// one pixel centre (MS: the pass's sample of the pixel): its camera ray (origin 0) against the triangle
+// (Moller-Trumbore); the nearest hit per pixel is kept by an atomic min of (depth bits << 32 | triangle
+// index)
+template <bool MS>
+__device__ __forceinline__ void tri_cover(const RenderArgsOf<MS>& a, const TriCam& T, unsigned j, int px, int py,
                                           float tanh_, float aspect, unsigned long long* vis, uint8_t* tflag) {
 #pragma clang fp contract(off)
   const int W = a.cam.width, H = a.cam.height;
+  const float ox = sample_x<MS>(a), oy = sample_y<MS>(a);
   {
-    const float cx = px + 0.5f, cy = py + 0.5f;
+    const float cx = px + ox, cy = py + oy;
     bool in = true;
 #pragma unroll
     for (int i = 0; i < 4; i++) in = in && (T.ea[i] * cx + T.eb[i] * cy + T.ec[i] >= 0.f);
@@ -560,7 +593,7 @@ __device__ __forceinline__ void tri_cover(const RenderArgs& a, const TriCam& T, 
   }
   // the pixel centre's ray (slopes by multiplication: no division per pixel)
   const float sx = tanh_ * aspect, sy = tanh_;
-  const float d[3] = {(px + 0.5f) * (2.0f * sx / W) - sx, sy - (py + 0.5f) * (2.0f * sy / H), -1.0f};
+  const float d[3] = {(px + ox) * (2.0f * sx / W) - sx, sy - (py + oy) * (2.0f * sy / H), -1.0f};
   const float* e1 = T.e1;
   const float* e2 = T.e2;
   const float p[3] = {d[1] * e2[2] - d[2] * e2[1], d[2] * e2[0] - d[0] * e2[2], d[0] * e2[1] - d[1] * e2[0]};
@@ -609,7 +642,8 @@ __device__ __forceinline__ void mesh_frames_block(const RenderArgs& a, int env, 
   __syncthreads();
 }
 
-__global__ void __launch_bounds__(RASTER_THREADS) raster_kernel(RenderArgs a, int chunks) {
+template <bool MS>
+__global__ void __launch_bounds__(RASTER_THREADS) raster_kernel(RenderArgsOf<MS> a, int chunks) {
   __shared__ CamFrame cf;
   __shared__ float mR[MAX_MESH][9], mc[MAX_MESH][3];
   __shared__ int mvis[MAX_MESH];
@@ -631,7 +665,7 @@ __global__ void __launch_bounds__(RASTER_THREADS) raster_kernel(RenderArgs a, in
   if (j < a.ntri) {
     const float4* tp = reinterpret_cast<const float4*>(a.mesh_tri) + 4 * (size_t)j;
     const int k = __float_as_int(tp[3].x) >> 16;
-    if (k >= 0 && k < a.nmesh && mvis[k]) tri_setup(a, tp, mR[k], mc[k], tanh_, aspect, T);
+    if (k >= 0 && k < a.nmesh && mvis[k]) tri_setup<MS>(a, tp, mR[k], mc[k], tanh_, aspect, T);
   }
   const bool live = T.x0 <= T.x1 && T.y0 <= T.y1 && !(a.dbg & 32);  // (dbg 32, timing probe: set-up only)
   if ((a.dbg & 32) && T.x0 == -12345) a.vis[0] = 0;  // (keeps the probe's set-up alive)
@@ -645,7 +679,7 @@ __global__ void __launch_bounds__(RASTER_THREADS) raster_kernel(RenderArgs a, in
   // max-scan through LDS per 64 centres -- measured 2x slower: latency-bound LDS round trips.)
   if (live && span <= RASTER_SMALL)
     for (int py = T.y0; py <= T.y1; ++py)
-      for (int px = T.x0; px <= T.x1; ++px) tri_cover(a, T, (unsigned)j, px, py, tanh_, aspect, vis, tflag);
+      for (int px = T.x0; px <= T.x1; ++px) tri_cover<MS>(a, T, (unsigned)j, px, py, tanh_, aspect, vis, tflag);
   unsigned long long bigs = __ballot(live && span > RASTER_SMALL);
   const int lane = threadIdx.x & 63;
   while (bigs) {
@@ -669,7 +703,7 @@ __global__ void __launch_bounds__(RASTER_THREADS) raster_kernel(RenderArgs a, in
     const int q = 64 / bnx, r = 64 - q * bnx;
     int yy = lane / bnx, xx = lane - yy * bnx;
     for (int i = lane; i < np; i += 64) {
-      tri_cover(a, B, jb, bx0 + xx, by0 + yy, tanh_, aspect, vis, tflag);
+      tri_cover<MS>(a, B, jb, bx0 + xx, by0 + yy, tanh_, aspect, vis, tflag);
       xx += r;
       yy += q;
       if (xx >= bnx) {
@@ -751,7 +785,9 @@ __device__ bool shadow_bvh(const float4* bvh_nodes, const int32_t* bvh_tri, cons
 // depth and hit_geom stay bit-identical to its (inlined, the primary rays' arithmetic was contracted
 // differently).  The LDS tables keep their address space through the call (no flat loads).
 typedef const __attribute__((address_space(3))) float lds_cf;
-template <bool VIS>
+// MS: the sample passes call a copy of their own, so the code of the single-sample instantiations'
+// callee (its register use is fitted to its callers) stays what it was
+template <bool VIS, bool MS = false>
 __device__ __attribute__((noinline)) bool shadow_occluded(const float4* bvh_nodes, const int32_t* bvh_tri,
                                                           const int32_t* bvh_root, const float* mesh_tri, int nmesh,
                                                           const PrimCam* prims, int np, lds_cf* sP, lds_cf* sPd,
@@ -805,6 +841,49 @@ __device__ __attribute__((noinline)) bool shadow_occluded(const float4* bvh_node
   return false;
 }
 
+// the policy input forms of one pixel from its 8-bit colour u (include/rmbx.h, rmbx_camera), for the
+// resolve: the stores at the end of render_kernel, which keeps them in line (called from there, this
+// function changed the register allocation -- the spills -- of the single-sample instantiations)
+__device__ __forceinline__ void store_policy(const RenderArgs& a, int env, int px, int py, int W, int H, size_t hw,
+                                             size_t pix, const uint8_t* u) {
+  if (a.policy_dtype == 2) {
+    // 2x2 space-to-depth [n][H/2][W/2][16]: channel (dy*2+dx)*3+c, 12..15 zero
+    const int Hs = H >> 1, Ws = W >> 1;
+    __hip_bfloat16* o = reinterpret_cast<__hip_bfloat16*>(a.policy) +
+                        (((size_t)env * Hs + (py >> 1)) * Ws + (px >> 1)) * 16;
+    const int q = ((py & 1) * 2 + (px & 1)) * 3;
+    for (int c = 0; c < 3; c++) o[q + c] = __float2bfloat16(((float)u[c] / 255.0f - a.cam.mean[c]) / a.cam.std[c]);
+    if ((py & 1) && (px & 1))
+      for (int c = 12; c < 16; c++) o[c] = __float2bfloat16(0.0f);
+  } else if (a.policy_dtype == 3) {
+    // the same space-to-depth layout in f32
+    const int Hs = H >> 1, Ws = W >> 1;
+    float* o = reinterpret_cast<float*>(a.policy) + (((size_t)env * Hs + (py >> 1)) * Ws + (px >> 1)) * 16;
+    const int q = ((py & 1) * 2 + (px & 1)) * 3;
+    for (int c = 0; c < 3; c++) o[q + c] = ((float)u[c] / 255.0f - a.cam.mean[c]) / a.cam.std[c];
+    if ((py & 1) && (px & 1))
+      for (int c = 12; c < 16; c++) o[c] = 0.0f;
+  } else if (a.policy_dtype == 4) {
+    // the same space-to-depth layout holding the 8-bit pixel values themselves (the f32 stem on
+    // the quantised image, rmbx_stem_s2d_conv_maxpool_u8, applies mean / std exactly)
+    const int Hs = H >> 1, Ws = W >> 1;
+    uint8_t* o = reinterpret_cast<uint8_t*>(a.policy) + (((size_t)env * Hs + (py >> 1)) * Ws + (px >> 1)) * 16;
+    const int q = ((py & 1) * 2 + (px & 1)) * 3;
+    for (int c = 0; c < 3; c++) o[q + c] = u[c];
+    if ((py & 1) && (px & 1))
+      for (int c = 12; c < 16; c++) o[c] = 0;
+  } else {
+    for (int c = 0; c < 3; c++) {
+      const float v = ((float)u[c] / 255.0f - a.cam.mean[c]) / a.cam.std[c];
+      const size_t idx = ((size_t)env * 3 + c) * hw + pix;
+      if (a.policy_dtype == 1)
+        reinterpret_cast<__hip_bfloat16*>(a.policy)[idx] = __float2bfloat16(v);
+      else
+        reinterpret_cast<float*>(a.policy)[idx] = v;
+    }
+  }
+}
+
 // RMBX_RENDER_MINW: minimum waves per SIMD the register allocation targets: 8 (default; 64
 // registers, 136 B/lane of spilled set-up values, none in the ray loop's hot path) -- per
 // 1024-env 8-bit frame 5.74-5.79 ms vs 6.46 at 5 waves (94 registers, no spills), 6.06 at 6,
@@ -823,8 +902,10 @@ __device__ __attribute__((noinline)) bool shadow_occluded(const float4* bvh_node
 #ifndef RMBX_RENDER_SH_MINW
 #define RMBX_RENDER_SH_MINW 4
 #endif
-template <bool VIS, int CM, bool SH = false>
-__global__ void __launch_bounds__(256, SH ? RMBX_RENDER_SH_MINW : RMBX_RENDER_MINW) render_kernel(RenderArgs a) {
+// MS: one sample pass of the 4-sample mode (CM 0 only): the rays go through the pass's sample position
+// instead of the pixel centre, and the only output is the 8-bit colour, summed into a.samp
+template <bool VIS, int CM, bool SH = false, bool MS = false>
+__global__ void __launch_bounds__(256, SH ? RMBX_RENDER_SH_MINW : RMBX_RENDER_MINW) render_kernel(RenderArgsOf<MS> a) {
   __shared__ PrimCam prims[MAX_PRIM];
   __shared__ int order[MAX_PRIM];        // the block's primitives sorted front to back, once
   __shared__ int tile_sorted[MAX_PRIM];  // the tile's survivors in that order
@@ -1069,8 +1150,8 @@ __global__ void __launch_bounds__(256, SH ? RMBX_RENDER_SH_MINW : RMBX_RENDER_MI
   __syncthreads();
   const int px = tx0 + (tid % RENDER_TILE), py = ty0 + (tid / RENDER_TILE);
   if (px < W && py < H) {
-  const float d[3] = {((2.0f * (px + 0.5f) / W) - 1.0f) * tanh_ * aspect,
-                      (1.0f - 2.0f * (py + 0.5f) / H) * tanh_, -1.0f};
+  const float d[3] = {((2.0f * (px + sample_x<MS>(a)) / W) - 1.0f) * tanh_ * aspect,
+                      (1.0f - 2.0f * (py + sample_y<MS>(a)) / H) * tanh_, -1.0f};
   const size_t pix = (size_t)py * W + px;
   // the mesh candidate (the visibility pass's nearest triangle), kept for the final pass
   float m_best = 1e30f, m_n[3] = {0, 0, 1}, m_rgb[3] = {0.f, 0.f, 0.f};
@@ -1199,7 +1280,7 @@ __global__ void __launch_bounds__(256, SH ? RMBX_RENDER_SH_MINW : RMBX_RENDER_MI
       // a receiver the light does not reach loses the light's two terms (0.3 ndl below and sp)
       if (ndl > 0.f) {
         const float O[3] = {best * d[0] + 1e-3f * L[0], best * d[1] + 1e-3f * L[1], best * d[2] + 1e-3f * L[2]};
-        if (shadow_occluded<VIS>(a.bvh_nodes, a.bvh_tri, a.bvh_root, a.mesh_tri, a.nmesh, prims, np, (lds_cf*)&sP[0][0],
+        if (shadow_occluded<VIS, MS>(a.bvh_nodes, a.bvh_tri, a.bvh_root, a.mesh_tri, a.nmesh, prims, np, (lds_cf*)&sP[0][0],
                                  (lds_cf*)sPd, mR, (lds_cf*)&mC[0][0], (lds_cf*)mCd, O, L))
           ndl = 0.f;
       }
@@ -1256,6 +1337,13 @@ __global__ void __launch_bounds__(256, SH ? RMBX_RENDER_SH_MINW : RMBX_RENDER_MI
     pixel_pass(1);
   }
   const bool do_store = !(a.dbg & 2) || col[0] == 12345.f;  // (diagnostic: keep the shading live)
+  if constexpr (MS) {
+    if (do_store) {
+      const uint32_t w = (uint32_t)u[0] | ((uint32_t)u[1] << 10) | ((uint32_t)u[2] << 20);
+      uint32_t* o = a.samp + (size_t)env * hw + pix;
+      *o = a.sfirst ? w : *o + w;
+    }
+  } else {
   if (a.rgb && do_store) {
     uint8_t* o = a.rgb + ((size_t)env * hw + pix) * 3;
     o[0] = u[0];
@@ -1302,10 +1390,35 @@ __global__ void __launch_bounds__(256, SH ? RMBX_RENDER_SH_MINW : RMBX_RENDER_MI
       }
     }
   }
+  }
   }  // pixel
   __syncthreads();
   if (VIS && tid == 0 && tile_vis) a.tflag[(size_t)env * ntiles + tile] = 0;
   }  // tiles
+}
+
+// 4 samples per pixel, the resolve: one thread per pixel averages the four 8-bit sample colours the
+// MS passes summed into a.samp, (s0 + s1 + s2 + s3 + 2) >> 2 per channel, and writes rgb and the
+// policy form from that 8-bit pixel as render_kernel does from its own
+__global__ void __launch_bounds__(256) resolve_kernel(RenderArgsMS a) {
+  const int W = a.cam.width, H = a.cam.height;
+  const size_t hw = (size_t)H * W;
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= hw * (size_t)a.n_env) return;
+  const int env = (int)(i / hw);
+  if (a.active && !a.active[env]) return;
+  const size_t pix = i - (size_t)env * hw;
+  const int py = (int)(pix / W), px = (int)(pix - (size_t)py * W);
+  const uint32_t w = a.samp[i];
+  const uint8_t u[3] = {(uint8_t)(((w & 1023u) + 2u) >> 2), (uint8_t)((((w >> 10) & 1023u) + 2u) >> 2),
+                        (uint8_t)((((w >> 20) & 1023u) + 2u) >> 2)};
+  if (a.rgb) {
+    uint8_t* o = a.rgb + i * 3;
+    o[0] = u[0];
+    o[1] = u[1];
+    o[2] = u[2];
+  }
+  if (a.policy) store_policy(a, env, px, py, W, H, hw, pix, u);
 }
 
 // Static-background cache validity, one wave per env: the camera body's pose and every static
@@ -1407,9 +1520,17 @@ extern "C" int rmbx_render_scene_cached(const rmbx_camera* cam, const rmbx_scene
   a.bvh_nodes = reinterpret_cast<const float4*>(scene->bvh_nodes);
   a.bvh_tri = scene->bvh_tri;
   a.bvh_root = scene->bvh_root;
+  // 4 samples per pixel: the colour outputs come from four sample passes and the resolve; depth and
+  // hit_geom from the ordinary pixel-centre pass, which then writes no colour
+  RMBX_CHECK_ARG(scene->samples == 0 || scene->samples == 1 || scene->samples == 4,
+                 "samples=%d: 1 (or 0) and 4 samples per pixel are implemented", scene->samples);
+  const bool ms = scene->samples == 4 && (rgb || policy_img);
+  RMBX_CHECK_ARG(!ms || (scene->samp && ((uintptr_t)scene->samp & 3) == 0), "samples=4 needs the samp workspace");
   const char* cache_env = std::getenv("RMBX_RENDER_CACHE");  // 0: render every pixel in full (A/B)
-  // (a shadowed render bypasses the cache: a moving body can shadow a cached static pixel)
-  const bool use_cache = cache && cache->nstatic > 0 && !shadows && !(cache_env && std::atoi(cache_env) == 0);
+  // (a shadowed render bypasses the cache: a moving body can shadow a cached static pixel; a 4-sample
+  // render too: the cache holds the pixel centres' static scene, not the samples')
+  const bool use_cache =
+      cache && cache->nstatic > 0 && !shadows && !ms && !(cache_env && std::atoi(cache_env) == 0);
   if (use_cache) {
     RMBX_CHECK_ARG(cache->prim_static && cache->static_prims && cache->cache && cache->snap && cache->dirty &&
                        ((uintptr_t)cache->cache & 7) == 0 && cache->nstatic <= scene->nprim,
@@ -1460,6 +1581,43 @@ extern "C" int rmbx_render_scene_cached(const rmbx_camera* cam, const rmbx_scene
   const size_t nblocks = (size_t)n_env * a.groups;
   RMBX_CHECK_ARG(nblocks < (1ull << 31), "grid too large");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int chunks = (scene->ntri + RASTER_THREADS - 1) / RASTER_THREADS;
+  const size_t rblocks = (size_t)chunks * n_env;
+  RMBX_CHECK_ARG(!meshes || rblocks < (1ull << 31), "raster grid too large");
+  const size_t pblocks = ((size_t)n_env * cam->width * cam->height + 255) / 256;
+  RMBX_CHECK_ARG(pblocks < (1ull << 31), "resolve grid too large");
+  if (ms) {
+    // one visibility + ray-cast pass per sample position (each leaves vis / tflag empty again), the
+    // 8-bit colours summed in samp; then the resolve
+    static const float pattern[4][2] = RMBX_SAMPLE_PATTERN;
+    rmbx::RenderArgsMS m;
+    static_cast<rmbx::RenderArgs&>(m) = a;
+    m.samp = scene->samp;
+    for (int k = 0; k < 4; k++) {
+      m.sox = pattern[k][0];
+      m.soy = pattern[k][1];
+      m.sfirst = k == 0;
+      if (meshes) {
+        hipLaunchKernelGGL(rmbx::raster_kernel<true>, dim3((unsigned)rblocks), dim3(RASTER_THREADS), 0, st, m, chunks);
+        RMBX_CHECK_LAUNCH();
+        if (shadows)
+          hipLaunchKernelGGL((rmbx::render_kernel<true, 0, true, true>), dim3((unsigned)nblocks), dim3(256), 0, st, m);
+        else
+          hipLaunchKernelGGL((rmbx::render_kernel<true, 0, false, true>), dim3((unsigned)nblocks), dim3(256), 0, st, m);
+      } else if (shadows) {
+        hipLaunchKernelGGL((rmbx::render_kernel<false, 0, true, true>), dim3((unsigned)nblocks), dim3(256), 0, st, m);
+      } else {
+        hipLaunchKernelGGL((rmbx::render_kernel<false, 0, false, true>), dim3((unsigned)nblocks), dim3(256), 0, st, m);
+      }
+      RMBX_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(rmbx::resolve_kernel, dim3((unsigned)pblocks), dim3(256), 0, st, m);
+    RMBX_CHECK_LAUNCH();
+    if (!depth && !hit_geom) return RMBX_OK;
+    a.rgb = nullptr;  // the pixel-centre pass below: depth and hit_geom only
+    a.policy = nullptr;
+  }
+  const bool shade_shadows = shadows && !ms;  // (the centre pass of a 4-sample render writes no colour)
   if (use_cache) {
     hipLaunchKernelGGL(rmbx::render_cache_check_kernel, dim3((unsigned)n_env), dim3(64), 0, st, a,
                        cache->static_prims, (int)cache->nstatic, cache->snap, cache->dirty);
@@ -1468,16 +1626,13 @@ extern "C" int rmbx_render_scene_cached(const rmbx_camera* cam, const rmbx_scene
   if (meshes) {
     // pass 1: the meshes' nearest triangle per pixel into the visibility buffer (empty on entry:
     // the ray-cast pass clears every key and tile flag it consumes)
-    const int chunks = (scene->ntri + RASTER_THREADS - 1) / RASTER_THREADS;
-    const size_t rblocks = (size_t)chunks * n_env;
-    RMBX_CHECK_ARG(rblocks < (1ull << 31), "raster grid too large");
-    hipLaunchKernelGGL(rmbx::raster_kernel, dim3((unsigned)rblocks), dim3(RASTER_THREADS), 0, st, a, chunks);
+    hipLaunchKernelGGL(rmbx::raster_kernel<false>, dim3((unsigned)rblocks), dim3(RASTER_THREADS), 0, st, a, chunks);
     RMBX_CHECK_LAUNCH();
     if (use_cache) {
       hipLaunchKernelGGL((rmbx::render_kernel<true, 1>), dim3((unsigned)nblocks), dim3(256), 0, st, a);
       RMBX_CHECK_LAUNCH();
       hipLaunchKernelGGL((rmbx::render_kernel<true, 2>), dim3((unsigned)nblocks), dim3(256), 0, st, a);
-    } else if (shadows) {
+    } else if (shade_shadows) {
       hipLaunchKernelGGL((rmbx::render_kernel<true, 0, true>), dim3((unsigned)nblocks), dim3(256), 0, st, a);
     } else {
       hipLaunchKernelGGL((rmbx::render_kernel<true, 0>), dim3((unsigned)nblocks), dim3(256), 0, st, a);
@@ -1486,7 +1641,7 @@ extern "C" int rmbx_render_scene_cached(const rmbx_camera* cam, const rmbx_scene
     hipLaunchKernelGGL((rmbx::render_kernel<false, 1>), dim3((unsigned)nblocks), dim3(256), 0, st, a);
     RMBX_CHECK_LAUNCH();
     hipLaunchKernelGGL((rmbx::render_kernel<false, 2>), dim3((unsigned)nblocks), dim3(256), 0, st, a);
-  } else if (shadows) {
+  } else if (shade_shadows) {
     hipLaunchKernelGGL((rmbx::render_kernel<false, 0, true>), dim3((unsigned)nblocks), dim3(256), 0, st, a);
   } else {
     hipLaunchKernelGGL((rmbx::render_kernel<false, 0>), dim3((unsigned)nblocks), dim3(256), 0, st, a);

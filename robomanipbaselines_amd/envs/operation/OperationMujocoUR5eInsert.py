@@ -11,6 +11,7 @@ class OperationMujocoUR5eInsert:
         self.env = BatchedMujocoUR5eInsertEnv(
             self.args.num_envs, self.args.device, world_random_scale=self.args.world_random_scale, seed=self.args.seed,
             env_offset=self.args.env_offset, shadows=getattr(self.args, "shadows", "off"),
+            offsamples=getattr(self.args, "offsamples", 1),
         )
 
     def get_pre_motion_phases(self):

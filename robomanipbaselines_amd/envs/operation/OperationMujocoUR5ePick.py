@@ -10,7 +10,8 @@ class OperationMujocoUR5ePick:
     def setup_env(self, render_mode=None):
         self.env = BatchedMujocoUR5ePickEnv(
             self.args.num_envs, self.args.device, world_random_scale=self.args.world_random_scale, seed=self.args.seed,
-            env_offset=self.args.env_offset, shadows=getattr(self.args, "shadows", "off"), tactile=getattr(self.args, "tactile", False),
+            env_offset=self.args.env_offset, shadows=getattr(self.args, "shadows", "off"),
+            offsamples=getattr(self.args, "offsamples", 1), tactile=getattr(self.args, "tactile", False),
         )
 
     def get_pre_motion_phases(self):

@@ -20,7 +20,7 @@ from .. import _native as N  # noqa: F401  (fails loudly if librmbx.so is missin
 from .. import kernels as K
 from .. import model as MD
 from ..engine import PhysicsEngine
-from ..render import Renderer, scene_casts_shadows
+from ..render import Renderer, samples_of, scene_casts_shadows, scene_offsamples
 
 ARM_JOINTS = ["shoulder_pan_joint", "shoulder_lift_joint", "elbow_joint", "wrist_1_joint", "wrist_2_joint", "wrist_3_joint"]
 GRIPPER_JOINTS = ["right_driver_joint", "right_spring_link_joint", "left_driver_joint", "left_spring_link_joint"]
@@ -63,10 +63,14 @@ class BatchedMujocoUR5eEnvBase:
     world_offsets = None  # [n_world, 3] offsets of world_body per world index
 
     def __init__(self, num_envs, device="cuda:0", world_random_scale=None, seed=0, image_size=(480, 640),
-                 model_name=None, env_offset=0, shadows="off"):
+                 model_name=None, env_offset=0, shadows="off", offsamples=1):
         """shadows: "off" (the default) or "scene": the renderer draws the hard shadows of the scene's
         light where the scene's <light> casts them (castshadow, MuJoCo's default: the Cable, Ring and
-        Pick scenes; the others declare castshadow="false" and render as with "off")."""
+        Pick scenes; the others declare castshadow="false" and render as with "off").
+        offsamples: samples per pixel of the camera images: 1 (the default), 4, or "scene" for the
+        scene's `<visual><quality offsamples>` (MuJoCo's default 4, what the reference's offscreen
+        renders have); depth images and point clouds stay the pixel centres'.  ValueError for a count
+        the renderer does not implement."""
         if shadows not in ("off", "scene"):
             raise ValueError(f"shadows must be 'off' or 'scene', not {shadows!r}")
         model_name = model_name or self.model_name
@@ -76,7 +80,11 @@ class BatchedMujocoUR5eEnvBase:
         self.info = MD.ModelInfo(self.arrays)
         self.engine = PhysicsEngine(self.arrays, self.num_envs, device)
         self.shadows = shadows == "scene" and scene_casts_shadows(self.arrays)
-        self.renderer = Renderer(self.arrays, device, width=image_size[1], height=image_size[0], shadows=self.shadows)
+        if isinstance(offsamples, str) and offsamples != "scene":
+            offsamples = int(offsamples)  # (the command line's "1" / "4")
+        self.offsamples = samples_of(scene_offsamples(self.arrays)) if offsamples == "scene" else offsamples
+        self.renderer = Renderer(self.arrays, device, width=image_size[1], height=image_size[0], shadows=self.shadows,
+                                 samples=self.offsamples)
         self.world_random_scale = world_random_scale
         self.seed = int(seed)
         # global index of local env 0 (the rank's shard start): noise streams are keyed by the

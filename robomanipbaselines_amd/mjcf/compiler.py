@@ -768,6 +768,12 @@ def compile_mjcf(path, missing_mesh_box=(0.045, 0.0125, 0.0125), convex_meshes=F
             for k in ("ambient", "diffuse", "specular"):
                 if k in hl.attrib:
                     M.headlight[k] = np.array(_floats(hl.attrib[k]))
+    # <visual><quality offsamples>: the multisampling of MuJoCo's offscreen buffer (mjVisual.quality's
+    # default, [ext] mujoco 3.1.6: 4)
+    M.offsamples = 4
+    for v in root.findall("visual"):
+        for q in v.findall("quality"):
+            M.offsamples = int(q.attrib.get("offsamples", M.offsamples))
 
     # ---- actuators, tendons, equality, sensors, excludes
     tendons = []
@@ -1116,3 +1122,9 @@ def light_arrays(M):
             "headlight_ambient": np.asarray(M.headlight["ambient"], np.float64),
             "headlight_diffuse": np.asarray(M.headlight["diffuse"], np.float64),
             "headlight_specular": np.asarray(M.headlight["specular"], np.float64)}
+
+
+def quality_arrays(M):
+    """quality_offsamples i32: the compiled model's <visual><quality offsamples>, the samples per pixel
+    of MuJoCo's offscreen buffer (render.scene_offsamples; `--offsamples scene`)."""
+    return {"quality_offsamples": np.int32(M.offsamples)}

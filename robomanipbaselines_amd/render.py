@@ -114,6 +114,29 @@ def scene_casts_shadows(arrays):
     return bool(np.any(np.asarray(arrays["light_castshadow"]) != 0))
 
 
+SAMPLES = (1, 4)  # samples per pixel the kernel implements (include/rmbx.h rmbx_scene_tables, "Samples")
+
+
+def scene_offsamples(arrays):
+    """The compiled scene's `<visual><quality offsamples>` (`--offsamples scene`): the multisampling of
+    the offscreen buffer the reference renders its camera images in.  MuJoCo's default is 4; a scene
+    compiled before the field existed (the shipped assets, none of whose files sets it) has it."""
+    if "quality_offsamples" not in arrays:
+        return 4
+    return int(np.asarray(arrays["quality_offsamples"]).reshape(-1)[0])
+
+
+def samples_of(value):
+    """Samples per pixel for a scene's offsamples value: 0 (no multisampling) and 1 are one sample, 4
+    is four; ValueError for a value the kernel does not implement."""
+    value = int(value)
+    if value in (0, 1):
+        return 1
+    if value in SAMPLES:
+        return value
+    raise ValueError(f"offsamples={value}: the renderer implements 1 and 4 samples per pixel (0 is taken as 1)")
+
+
 def shadow_light(arrays):
     """The unit vector towards the light whose shadows the renderer draws, world frame.  The shading
     constants are hard-coded in the kernel, so a scene that carries its light arrays
@@ -140,11 +163,17 @@ def shadow_light(arrays):
 
 
 class Renderer:
-    def __init__(self, arrays, device, width=640, height=480, shadows=False):
+    def __init__(self, arrays, device, width=640, height=480, shadows=False, samples=1):
         """shadows: hard shadows of the scene's directional light (include/rmbx.h rmbx_scene_tables);
-        a shadowed render does not use the static-background cache."""
+        a shadowed render does not use the static-background cache.  samples: 1, or 4 samples per
+        pixel averaged into every colour output (the same header, "Samples"); depth and hit_geom stay
+        the pixel centre's; a 4-sample render does not use the cache either."""
+        if isinstance(samples, bool) or samples not in SAMPLES:
+            raise ValueError(f"samples={samples!r}: 1 or 4 samples per pixel")
         self.arrays = arrays
         self.shadows = bool(shadows)
+        self.samples = int(samples)
+        self._samp = None  # 4 samples: the sample sums u32 [n, H, W], allocated at the first render
         pi, pf = build_prims(arrays)
         self.nprim = len(pi)
         self.prim_i32 = torch.tensor(pi, device=device)
@@ -215,6 +244,7 @@ class Renderer:
                 self.bvh_root = torch.tensor(t["bvh_root"], device=device)
                 sc.bvh_nodes, sc.bvh_tri, sc.bvh_root = (self.bvh_nodes.data_ptr(), self.bvh_tri.data_ptr(),
                                                          self.bvh_root.data_ptr())
+        sc.samples = self.samples
         self._scene = sc
         # static-background caches (rmbx_render_scene_cached): the primitives of bodies welded to the
         # world, one cache per world-fixed camera (allocated at its first render)
@@ -252,9 +282,10 @@ class Renderer:
 
     def _cache(self, camera_name, cam, n):
         """The static-background cache of a world-fixed camera (include/rmbx.h rmbx_render_cache), or
-        None (a camera on a moving body, a scene without static primitives, a shadowed render, or
-        RMBX_RENDER_CACHE=0: the call would ignore it, so its n * H * W * 8 bytes are not allocated)."""
-        if self.shadows or os.environ.get("RMBX_RENDER_CACHE", "").strip() == "0":
+        None (a camera on a moving body, a scene without static primitives, a shadowed or 4-sample
+        render, or RMBX_RENDER_CACHE=0: the call would ignore it, so its n * H * W * 8 bytes are not
+        allocated)."""
+        if self.shadows or self.samples != 1 or os.environ.get("RMBX_RENDER_CACHE", "").strip() == "0":
             return None
         nst = int(self.static_prims.numel())
         weld = self.arrays["body_weldid"] if "body_weldid" in self.arrays else None
@@ -307,6 +338,10 @@ class Renderer:
                 self._vis = torch.full((n * H * W,), -1, dtype=torch.int64, device=self.device)
                 self._tflag = torch.zeros(n * ntiles, dtype=torch.uint8, device=self.device)
             self._scene.vis, self._scene.tflag = self._vis.data_ptr(), self._tflag.data_ptr()
+        if self.samples == 4 and (rgb is not None or policy is not None):
+            if self._samp is None or self._samp.shape[0] < n * H * W:
+                self._samp = torch.empty(n * H * W, dtype=torch.int32, device=self.device)
+            self._scene.samp = self._samp.data_ptr()
         cache = self._cache(camera_name, cam, n)
         try:
             N.call("rmbx_render_scene_cached", ctypes.byref(cam), ctypes.byref(self._scene),

@@ -8,7 +8,8 @@ ms per batched infer_policy call.
   env-step (--tactile; the reference's tactile plugin is absent, envs/ur5e_pick.py);
 * Mlp on the cable scene;
 * Sarnn on the cable scene (fp32; RMBX_SARNN_FUSED=0 times the unfused torch route);
-* Act on the cable scene (bench.py's workload through this loop: the A/B of --shadows off / scene).
+* Act on the cable scene (bench.py's workload through this loop: the A/B of --shadows off / scene and of
+  --offsamples 1 / 4).
 
     python scripts/bench_policy.py DiffusionPolicy --num_envs 2048 --steps 24 --warmup 8
     python scripts/bench_policy.py DiffusionPolicy3d --num_envs 1024 --tactile
@@ -57,6 +58,8 @@ def main():
     p.add_argument("--env", choices=sorted(ENVS), default=None, help="default: the BASELINE config's scene")
     p.add_argument("--tactile", action="store_true", help="synthetic tactile every env-step (Pick scene)")
     p.add_argument("--shadows", choices=["off", "scene"], default="off", help="the renderer's shadows (Rollout.py --shadows)")
+    p.add_argument("--offsamples", choices=["1", "4", "scene"], default="1",
+                   help="samples per pixel of the camera images (Rollout.py --offsamples)")
     a = p.parse_args()
     a.env = a.env or DEFAULT_ENV[a.policy]
     a.precision = a.precision or ("fp32" if a.policy == "Sarnn" else "bf16")
@@ -70,7 +73,7 @@ def main():
 
     argv = ["--num_envs", str(a.num_envs), "--device", "cuda:0", "--world_idx_list", *[str(i) for i in range(6)],
             "--world_random_scale", "0.01", "0.01", "0.0", "--seed", "0", "--precision", a.precision,
-            "--shadows", a.shadows] + (["--tactile"] if a.tactile else [])
+            "--shadows", a.shadows, "--offsamples", a.offsamples] + (["--tactile"] if a.tactile else [])
     t_start = time.time()
 
     def log(msg):
@@ -118,6 +121,7 @@ def main():
                       "infer_ms_per_call": round(float(np.mean(inf)), 3) if inf else None,
                       "scene": a.env + (" minus YCB_sim" if a.env == "MujocoUR5ePick" else ""),
                       "tactile": "synthetic, every env-step" if a.tactile else None, "shadows": a.shadows,
+                      "offsamples": a.offsamples,
                       "data": "synthetic (random-init weights)"}), flush=True)
 
 

@@ -107,6 +107,8 @@ if __name__ == "__main__":
         arrays.update(C.visual_arrays(M))
         # the scene's lights (the renderer's shadows)
         arrays.update(C.light_arrays(M))
+        # the offscreen buffer's samples per pixel (--offsamples scene)
+        arrays.update(C.quality_arrays(M))
         out = os.path.join(MD.ASSET_DIR, name + ".npz")
         MD.save(arrays, out)
         print(name, "nq", M.nq, "nv", M.nv, "pairs", len(M.pairs), "->", out, os.path.getsize(out), "bytes")
