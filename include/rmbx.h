@@ -269,6 +269,89 @@ int rmbx_sched_close_bad(rmbx_sched_t* sched, const double* time, const int32_t*
                          double* last_elapsed, int n_pre, int n_env, void* stream);
 int rmbx_episode_recycle(const rmbx_stream_buffers* bufs, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Episode trace (--trace_dir): a device-side flight recorder of the env-steps of chosen episodes.
+ * Called once per env-step, after the physics step, rmbx_sched_update and (streaming)
+ * rmbx_sched_close_bad, and before the step mask is recomputed and before any recycle: a slot
+ * then still holds the poses of the step it just took.  An episode ends with the step whose
+ * rmbx_sched_update moves the slot past RolloutPhase (phase > n_pre: its results are recorded and
+ * the step mask drops it; `done` itself follows one call later, on a step the slot no longer
+ * takes) or whose rmbx_sched_close_bad closes it (done at once): ended = done or phase > n_pre.
+ * A row holds what the renderer reads (gxpos, gxmat, xpos, xquat: a slice of rows of the chunk is
+ * a batch the renderer can draw, with time as the batch dimension) and the state beside it.
+ *
+ * The chunk is a set of structure-of-arrays buffers of `capacity` rows, each array contiguous
+ * [capacity][...]; rows = {rows used, overflow}.  The caller reads the used rows and sets rows[0]
+ * back to 0 (every 16 steps with capacity = 16 n_env, so overflow only means a skipped flush).
+ *
+ * Row rule, slots visited in increasing order:
+ *  1. ep = slot_episode[s] (slot_episode NULL: episode_base + s, a lockstep run).  The slot is
+ *     skipped if ep < 0, if stepped is given and stepped[s] == 0, or if select is given and
+ *     select[ep - episode_base] == 0 (or ep - episode_base is outside [0, n_episodes)).
+ *  2. trace_episode[s] != ep: trace_episode[s] = ep, trace_step[s] = 0  (a new episode in the
+ *     slot; trace_episode starts at -1).
+ *  3. k = ++trace_step[s]: the env-steps the episode has taken.  It advances on every stepped
+ *     step, whether or not a row is written.
+ *  4. A row is written iff k % stride == 0 or the episode ended with this step: an episode's last
+ *     step is always kept.
+ *  5. The row goes at rows[0] + (number of earlier slots writing a row in this call): rows are
+ *     step-major and in slot order.  The index is an exclusive prefix sum over chunks of 256
+ *     slots with a running base (one workgroup, no atomics: the order is reproducible).
+ *  6. A row that would pass `capacity` is not written and sets rows[1] = 1 (which stays set);
+ *     rows[0] never exceeds capacity and nothing past the chunk is touched.
+ * Row fields: episode = ep, slot = s, step = k, phase / rollout_time_idx = the schedule's, flags =
+ * bit 0 done (ended, above), bit 1 success (the schedule's), bit 2 closed by a bad state (ended and
+ * bad_resets[s] > 0; bad_resets NULL: never), time[s], reward[s], and the slot's rows of ctrl (nu of
+ * ctrl_stride), qpos, qvel, gxpos, gxmat, xpos, xquat, copied bit for bit.
+ * slot_row i32 [n_env] is workspace: the row each slot wrote in this call, -1 = none; the copy
+ * runs on a grid of its own over (slot, array) with 16-byte accesses where source and destination
+ * are both 16-byte aligned, 8-byte otherwise.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct rmbx_trace_buffers {
+  const rmbx_sched_t* sched;     /* [n_env] */
+  const int32_t* slot_episode;   /* [n_env] or NULL */
+  const uint8_t* stepped;        /* [n_env] or NULL = all */
+  const uint8_t* select;         /* [n_episodes] or NULL = every episode */
+  const int32_t* bad_resets;     /* [n_env] or NULL */
+  const double* time;            /* [n_env] */
+  const double* reward;          /* [n_env] */
+  const double* ctrl;            /* [n_env][ctrl_stride] */
+  const double* qpos;            /* [n_env][nq] */
+  const double* qvel;            /* [n_env][nv] */
+  const double* gxpos;           /* [n_env][ngeom][3] */
+  const double* gxmat;           /* [n_env][ngeom][9] */
+  const double* xpos;            /* [n_env][nbody][3] */
+  const double* xquat;           /* [n_env][nbody][4] */
+  int32_t* trace_episode;        /* [n_env] kernel-owned, initialised to -1 */
+  int32_t* trace_step;           /* [n_env] kernel-owned */
+  int32_t* slot_row;             /* [n_env] workspace */
+  int32_t* out_episode;          /* the chunk: [capacity] each */
+  int32_t* out_slot;
+  int32_t* out_step;
+  int32_t* out_phase;
+  int32_t* out_rollout_time_idx;
+  uint8_t* out_flags;
+  double* out_time;
+  double* out_reward;
+  double* out_ctrl;              /* [capacity][nu] */
+  double* out_qpos;              /* [capacity][nq] */
+  double* out_qvel;              /* [capacity][nv] */
+  double* out_gxpos;             /* [capacity][ngeom][3] */
+  double* out_gxmat;             /* [capacity][ngeom][9] */
+  double* out_xpos;              /* [capacity][nbody][3] */
+  double* out_xquat;             /* [capacity][nbody][4] */
+  int32_t* rows;                 /* [2] {rows used, overflow} */
+  int32_t n_env, n_episodes, episode_base, stride, capacity;
+  int32_t n_pre;                 /* phase index of RolloutPhase, as rmbx_sched_active's */
+  int32_t nq, nv, nu, ctrl_stride, ngeom, nbody;
+} rmbx_trace_buffers;
+
+#define RMBX_TRACE_DONE 1
+#define RMBX_TRACE_SUCCESS 2
+#define RMBX_TRACE_BAD_STATE 4
+
+int rmbx_episode_trace(const rmbx_trace_buffers* bufs, void* stream);
+
 
 /* ---------------------------------------------------------------------------------------------
  * Batched MuJoCo-subset physics engine (the env.step hot path).

@@ -44,6 +44,7 @@ SIGNATURES = {
     "rmbx_sched_phases": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_p]),
     "rmbx_sched_close_bad": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_p]),
     "rmbx_episode_recycle": (_c_int, [_c_p, _c_p]),
+    "rmbx_episode_trace": (_c_int, [_c_p, _c_p]),
     "rmbx_engine_create": (_c_int, [_c_p, _c_int, _c_p]),
     "rmbx_engine_destroy": (_c_int, [_c_p]),
     "rmbx_engine_workspace_bytes": (_c_int, [_c_p, _c_p]),
@@ -169,6 +170,22 @@ class StreamBuffers(ctypes.Structure):
                 + [(n, ctypes.c_int32) for n in ("n_env", "n_episodes", "episode_base", "nq", "nv", "nu",
                                                  "ctrl_stride", "nbody", "world_body", "world_qadr")])
 
+
+class TraceBuffers(ctypes.Structure):
+    """ctypes mirror of rmbx_trace_buffers (include/rmbx.h)."""
+
+    _fields_ = ([(n, _c_p) for n in ("sched", "slot_episode", "stepped", "select", "bad_resets", "time", "reward",
+                                     "ctrl", "qpos", "qvel", "gxpos", "gxmat", "xpos", "xquat", "trace_episode",
+                                     "trace_step", "slot_row", "out_episode", "out_slot", "out_step", "out_phase",
+                                     "out_rollout_time_idx", "out_flags", "out_time", "out_reward", "out_ctrl",
+                                     "out_qpos", "out_qvel", "out_gxpos", "out_gxmat", "out_xpos", "out_xquat",
+                                     "rows")]
+                + [(n, ctypes.c_int32) for n in ("n_env", "n_episodes", "episode_base", "stride", "capacity", "n_pre",
+                                                 "nq", "nv", "nu", "ctrl_stride", "ngeom", "nbody")])
+
+
+# flags of a trace row (include/rmbx.h RMBX_TRACE_*)
+TRACE_DONE, TRACE_SUCCESS, TRACE_BAD_STATE = 1, 2, 4
 
 # numpy mirror of rmbx_sched_t (include/rmbx.h)
 TEX_LEVELS = 16  # include/rmbx.h RMBX_TEX_LEVELS

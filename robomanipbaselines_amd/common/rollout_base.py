@@ -35,6 +35,7 @@ import yaml
 from .. import kernels as K
 from ..common.data_key import DataKey, action_key_codes, state_key_codes
 from ..common.data_utils import make_meta_info
+from ..common.episode_trace import TraceWriter, parse_episodes, row_bytes, select_mask
 
 
 class PhaseSpec:
@@ -72,6 +73,7 @@ class BatchedRolloutBase:
         self.datetime_now = datetime.datetime.now()
         self._active = None  # optional caller override of the per-env step mask
         self.phase_timer = None  # optional PhaseTimer (common/phase_timer.py): bench.py's per-phase split
+        self._trace = None  # the TraceWriter of a run with --trace_dir
 
     def attach_phase_timer(self, timer):
         """Record HIP events at the policy / render / physics / glue boundaries of every env-step
@@ -144,6 +146,16 @@ class BatchedRolloutBase:
         parser.add_argument("--episode_offset", type=int, default=0,
                             help="global index of this process's first episode (its shard start under --num_gpus), "
                                  "the role --env_offset plays for envs")
+        parser.add_argument("--trace_dir", type=str, default=None,
+                            help="record the trajectory of every traced episode on the device and write it "
+                                 "here (common/episode_trace.py); bin/Replay.py renders any recorded step, the "
+                                 "last frame of a streamed episode included. Under --num_gpus each rank writes "
+                                 "rank<r>/ below it")
+        parser.add_argument("--trace_episodes", type=str, nargs="+", default=["all"],
+                            help="with --trace_dir: `all` or the global indices of the episodes to record")
+        parser.add_argument("--trace_stride", type=int, default=1,
+                            help="with --trace_dir: keep every K-th env-step of an episode and its last step; "
+                                 "K = --skip keeps the steps whose frames the policy read")
         if self.require_task_desc:
             parser.add_argument("--task_desc", type=str, required=True)
         self.set_additional_args(parser)
@@ -157,6 +169,9 @@ class BatchedRolloutBase:
         if self.args.world_random_scale is not None:
             self.args.world_random_scale = np.array(self.args.world_random_scale)
         self.args.auto_exit = True  # headless batched evaluation always auto-exits
+        if self.args.trace_stride < 1:
+            raise ValueError("--trace_stride must be at least 1")
+        parse_episodes(self.args.trace_episodes)  # ValueError for anything but `all` or indices
         if self.args.num_episodes is not None:
             if self.args.num_episodes < 1:
                 raise ValueError("--num_episodes must be at least 1")
@@ -342,6 +357,73 @@ class BatchedRolloutBase:
         self.rollout_time_idx = 0
         self.policy_action = torch.zeros((self.n, self.action_dim), dtype=torch.float64, device=dev)
         self.reset_variables()
+        if getattr(self.args, "trace_dir", None) and self.args.num_episodes is None:
+            self._trace_begin()
+
+    # -- episode trace (--trace_dir) -------------------------------------------------------------
+    def _trace_begin(self):
+        """Allocate the device trace of this run and open its directory.  Lockstep: env e is episode
+        env_offset + e; streaming: the slot -> episode map of the stream."""
+        from .. import kernels as K
+
+        a, env, eng = self.args, self.env, self.env.engine
+        old = getattr(self, "_trace", None)
+        if old is not None:
+            old.abort()
+        streaming = a.num_episodes is not None
+        base = int(a.episode_offset) if streaming else int(a.env_offset)
+        count = int(a.num_episodes) if streaming else self.n
+        chosen = parse_episodes(a.trace_episodes)
+        mask = select_mask(chosen, base, count)
+        select = None if mask is None else torch.tensor(mask, dtype=torch.uint8, device=self.device)
+        trace = K.EpisodeTrace(self.sched, eng, count, len(self.pre_durations), episode_base=base,
+                               slot_episode=self.stream.slot_episode if streaming else None, select=select,
+                               stride=a.trace_stride, bad_resets=env.bad_resets if streaming else None)
+        rank, world = self._dist_world()
+        directory = os.path.join(a.trace_dir, f"rank{rank}") if world > 1 else a.trace_dir
+        scale = a.world_random_scale
+        header = {
+            "policy": self.policy_name, "env": env.demo_name, "model_name": env.model_name,
+            "image_size": [int(env.renderer.height), int(env.renderer.width)], "camera_names": list(env.camera_names),
+            "seed": int(a.seed), "world_idx_list": [int(w) for w in a.world_idx_list],
+            "world_random_scale": None if scale is None else [float(x) for x in np.asarray(scale).reshape(-1)],
+            "skip": int(a.skip), "stride": int(a.trace_stride), "shadows": str(getattr(a, "shadows", "off")),
+            "offsamples": str(getattr(a, "offsamples", "1")), "dims": trace.dims, "streaming": streaming, "episode_base": base,
+            "num_episodes": count, "num_slots": self.n, "trace_episodes": "all" if chosen is None else chosen,
+            "max_duration": float(a.max_duration), "rank": rank, "world_size": world,
+        }
+        self._trace = TraceWriter(directory, header, trace)
+        # the size the run can reach: an episode ends by max_duration + the post-success second
+        dt = env.frame_skip * env.sim_timestep
+        steps = self._phase_entry_steps()[-1] + int(np.ceil((a.max_duration + 1.0) / dt)) + 1
+        if a.max_steps:
+            steps = min(steps, int(a.max_steps))
+        rows = steps // trace.stride + 1
+        traced = count if mask is None else int(mask.sum())
+        rb = row_bytes(trace.dims)
+        print(f"[{self.__class__.__name__}] Episode trace: {directory}: {rb} bytes per row x up to {rows} rows per "
+              f"episode (stride {trace.stride}) x {traced} episodes = up to {rb * rows * traced / 2**20:.1f} MiB",
+              flush=True)
+
+    def _trace_finish(self, records):
+        tr = getattr(self, "_trace", None)
+        if tr is not None:
+            self._trace = None
+            tr.finish(records)
+            self.last_trace = tr  # its counters (rows, flush times) outlive the run
+
+    def _lockstep_records(self, v):
+        """The records of a lockstep run in the form a streaming run keeps them (_native.EPISODE_DTYPE)."""
+        from .. import _native as N
+
+        rec = np.zeros(self.n, dtype=N.EPISODE_DTYPE)
+        rec["episode"] = self.args.env_offset + np.arange(self.n)
+        rec["slot"] = np.arange(self.n)
+        rec["world_idx"] = np.asarray(self.world_idx)
+        rec["rollout_time_idx"], rec["success"] = v["rollout_time_idx"], v["success"]
+        rec["bad_state"] = (self.env.bad_resets.cpu().numpy() > 0).astype(np.uint8)
+        rec["reward"], rec["duration"] = v["result_reward"], v["duration"]
+        return rec
 
     def _pre_update(self):
         n_pre = len(self.pre_durations)
@@ -413,6 +495,8 @@ class BatchedRolloutBase:
         for _ in range(self.env.frame_skip):
             self.host_time += self.env.sim_timestep
         K.sched_update(self.sched, self.env.get_time(), self.reward, self._pre, self.args.max_duration)
+        if getattr(self, "_trace", None) is not None:
+            self._trace.step(active, self.reward)
         K.sched_active(self.sched, len(self.pre_durations), out=self._step_mask)
         self._host_transition()
 
@@ -485,6 +569,8 @@ class BatchedRolloutBase:
         self._grip_values = {}
         self._g = 0  # global env-step index
         self.episode_records = None
+        if getattr(self.args, "trace_dir", None):
+            self._trace_begin()
 
     def _reach_target(self, ph):
         """(R [n, 9], p [n, 3]) a reach phase would set now for every slot."""
@@ -529,6 +615,8 @@ class BatchedRolloutBase:
         self.obs, self.reward, _, _, self.info = self.env.step(self.env_action(), active=self._step_mask)
         K.sched_update(self.sched, self.env.get_time(), self.reward, self._pre, self.args.max_duration)
         st.close_bad(n_pre)
+        if getattr(self, "_trace", None) is not None:
+            self._trace.step(self._step_mask, self.reward)
         K.sched_active(self.sched, n_pre, out=self._step_mask)
         # 4. recycle on aligned steps, then the phase report
         if (g + 1) % P == 0:
@@ -597,6 +685,8 @@ class BatchedRolloutBase:
             return self._finish_streaming()
         v = K.sched_view(self.sched)
         succ, rew, dur = v["success"].astype(bool), v["result_reward"].astype(np.float64), v["duration"]
+        if getattr(self, "_trace", None) is not None:
+            self._trace_finish(self._lockstep_records(v))
         rank, world = self._dist_world()
         if world > 1:
             import torch.distributed as dist
@@ -628,6 +718,8 @@ class BatchedRolloutBase:
         and rank 0 reports them in global episode order."""
         rec = self.stream.records()
         self.episode_records = rec
+        if getattr(self, "_trace", None) is not None:
+            self._trace_finish(rec)
         self.bad_state_episodes = int(rec["bad_state"].sum())
         succ, rew, dur = rec["success"].astype(bool), rec["reward"].copy(), rec["duration"].copy()
         nbad = self.bad_state_episodes

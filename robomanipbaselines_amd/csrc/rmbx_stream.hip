@@ -4,6 +4,10 @@
 // Latency-bound bookkeeping over n_env slots: plain C++, no atomics, vector stores only.  The
 // recycle runs as ONE workgroup that walks the slots in chunks of 256 with a running base, so the
 // slot -> episode assignment is the exclusive prefix sum of the done flags in slot order.
+//
+// Episode trace (--trace_dir, rmbx_episode_trace): the same one-workgroup scan gives every slot
+// that keeps this step its row of the chunk; the rows themselves (about 14 KB each in the Cable
+// scene, up to n_env of them per step) are copied by a second kernel on a grid of its own.
 
 #include <cstring>
 
@@ -148,6 +152,140 @@ __global__ void __launch_bounds__(kChunk) episode_recycle_kernel(rmbx_stream_buf
   }
 }
 
+// Row index of every slot (the row rule of include/rmbx.h) and the scalar fields of the rows.
+__global__ void __launch_bounds__(kChunk) episode_trace_index_kernel(rmbx_trace_buffers b) {
+  __shared__ int32_t scan[kChunk];
+  const int t = threadIdx.x;
+  const int32_t used0 = b.rows[0];
+  __syncthreads();  // every thread has read the counter before thread 0 rewrites it
+  int32_t base = 0;
+  for (int c0 = 0; c0 < b.n_env; c0 += kChunk) {
+    const int s = c0 + t;
+    int32_t ep = -1, k = 0;
+    bool keep = false, ended = false;
+    rmbx_sched_t v;
+    memset(&v, 0, sizeof(v));
+    if (s < b.n_env) {
+      ep = b.slot_episode ? b.slot_episode[s] : b.episode_base + s;
+      bool take = ep >= 0 && (!b.stepped || b.stepped[s] != 0);
+      if (take && b.select) {
+        const int64_t local = (int64_t)ep - b.episode_base;
+        take = local >= 0 && local < b.n_episodes && b.select[local] != 0;
+      }
+      if (take) {
+        if (b.trace_episode[s] != ep) {
+          b.trace_episode[s] = ep;
+          k = 0;
+        } else {
+          k = b.trace_step[s];
+        }
+        k += 1;
+        b.trace_step[s] = k;
+        v = b.sched[s];
+        ended = v.done != 0 || v.phase > b.n_pre;
+        keep = k % b.stride == 0 || ended;
+      }
+    }
+    const int32_t flag = keep ? 1 : 0;
+    // inclusive Hillis-Steele scan of the flags
+    scan[t] = flag;
+    __syncthreads();
+    for (int off = 1; off < kChunk; off <<= 1) {
+      const int32_t add = t >= off ? scan[t - off] : 0;
+      __syncthreads();
+      scan[t] += add;
+      __syncthreads();
+    }
+    const int32_t count = scan[kChunk - 1];
+    const int32_t rank = scan[t] - flag;  // exclusive, within the chunk
+    if (s < b.n_env) {
+      int32_t row = -1;
+      if (keep) {
+        const int64_t r = (int64_t)used0 + base + rank;
+        if (r >= 0 && r < b.capacity) {
+          row = (int32_t)r;
+          b.out_episode[row] = ep;
+          b.out_slot[row] = s;
+          b.out_step[row] = k;
+          b.out_phase[row] = v.phase;
+          b.out_rollout_time_idx[row] = v.rollout_time_idx;
+          uint8_t f = 0;
+          if (ended) f |= RMBX_TRACE_DONE;
+          if (v.success) f |= RMBX_TRACE_SUCCESS;
+          if (ended && b.bad_resets && b.bad_resets[s] > 0) f |= RMBX_TRACE_BAD_STATE;
+          b.out_flags[row] = f;
+          b.out_time[row] = b.time[s];
+          b.out_reward[row] = b.reward[s];
+        }
+      }
+      b.slot_row[s] = row;
+    }
+    base += count;
+    __syncthreads();  // the scan array is rewritten by the next chunk
+  }
+  if (t == 0) {
+    const int64_t total = (int64_t)used0 + base;
+    if (total > b.capacity) {
+      b.rows[0] = b.capacity;
+      b.rows[1] = 1;
+    } else {
+      b.rows[0] = (int32_t)total;
+    }
+  }
+}
+
+struct alignas(16) trace_u128 {
+  uint64_t lo, hi;
+};
+
+// len 8-byte words from src to dst by the nt threads of a block.  Both rows start on 8 bytes; where
+// they sit alike within 16 bytes (always, for an even row length on 16-byte aligned arrays) one
+// leading word brings both to a 16-byte boundary, the body moves 16 bytes per access and an odd
+// last word follows; rows that sit differently (odd length, slot and row of different parity) move
+// 8 bytes per access.
+__device__ __forceinline__ void trace_copy_words(const double* __restrict__ src, double* __restrict__ dst, int len,
+                                                 int t, int nt) {
+  const uint64_t* s = reinterpret_cast<const uint64_t*>(src);
+  uint64_t* d = reinterpret_cast<uint64_t*>(dst);
+  const uintptr_t sa = reinterpret_cast<uintptr_t>(s), da = reinterpret_cast<uintptr_t>(d);
+  if (((sa ^ da) & 15) == 0) {
+    int head = (sa & 15) ? 1 : 0;
+    if (head > len) head = len;
+    const int pairs = (len - head) >> 1;
+    const trace_u128* s2 = reinterpret_cast<const trace_u128*>(s + head);
+    trace_u128* d2 = reinterpret_cast<trace_u128*>(d + head);
+    for (int i = t; i < pairs; i += nt) d2[i] = s2[i];
+    if (t == 0 && head) d[0] = s[0];
+    if (t == nt - 1 && head + 2 * pairs < len) d[len - 1] = s[len - 1];
+  } else {
+    for (int i = t; i < len; i += nt) d[i] = s[i];
+  }
+}
+
+constexpr int kTraceArrays = 7;  // ctrl, qpos, qvel, gxpos, gxmat, xpos, xquat
+constexpr int kTraceThreads = 256;
+
+// Block (s, a) copies array a of slot s to the row the index kernel gave the slot.
+__global__ void __launch_bounds__(kTraceThreads) episode_trace_copy_kernel(rmbx_trace_buffers b) {
+  const int s = blockIdx.x;
+  const int32_t row = b.slot_row[s];
+  if (row < 0) return;
+  const double* src;
+  double* dst;
+  int len;
+  size_t src_stride;
+  switch (blockIdx.y) {
+    case 0: src = b.ctrl; dst = b.out_ctrl; len = b.nu; src_stride = b.ctrl_stride; break;
+    case 1: src = b.qpos; dst = b.out_qpos; len = b.nq; src_stride = b.nq; break;
+    case 2: src = b.qvel; dst = b.out_qvel; len = b.nv; src_stride = b.nv; break;
+    case 3: src = b.gxpos; dst = b.out_gxpos; len = b.ngeom * 3; src_stride = len; break;
+    case 4: src = b.gxmat; dst = b.out_gxmat; len = b.ngeom * 9; src_stride = len; break;
+    case 5: src = b.xpos; dst = b.out_xpos; len = b.nbody * 3; src_stride = len; break;
+    default: src = b.xquat; dst = b.out_xquat; len = b.nbody * 4; src_stride = len; break;
+  }
+  trace_copy_words(src + (size_t)s * src_stride, dst + (size_t)row * len, len, threadIdx.x, kTraceThreads);
+}
+
 }  // namespace rmbx
 
 using namespace rmbx;
@@ -194,6 +332,32 @@ int rmbx_episode_recycle(const rmbx_stream_buffers* b, void* stream) {
   RMBX_CHECK_ARG(b->world_body < 0 || b->world_qadr < 0, "rmbx_episode_recycle: world_body and world_qadr both set");
   if (b->n_env == 0) return RMBX_OK;
   hipLaunchKernelGGL(episode_recycle_kernel, dim3(1), dim3(kChunk), 0, stream_of(stream), *b);
+  RMBX_CHECK_LAUNCH();
+  return RMBX_OK;
+}
+
+int rmbx_episode_trace(const rmbx_trace_buffers* b, void* stream) {
+  RMBX_CHECK_ARG(b != nullptr, "rmbx_episode_trace: bufs is NULL");
+  RMBX_CHECK_ARG(b->sched && b->time && b->reward, "rmbx_episode_trace: a schedule / time / reward pointer is NULL");
+  RMBX_CHECK_ARG(b->ctrl && b->qpos && b->qvel && b->gxpos && b->gxmat && b->xpos && b->xquat,
+                 "rmbx_episode_trace: an engine pointer is NULL");
+  RMBX_CHECK_ARG(b->trace_episode && b->trace_step && b->slot_row, "rmbx_episode_trace: a per-slot state pointer is NULL");
+  RMBX_CHECK_ARG(b->out_episode && b->out_slot && b->out_step && b->out_phase && b->out_rollout_time_idx &&
+                     b->out_flags && b->out_time && b->out_reward && b->out_ctrl && b->out_qpos && b->out_qvel &&
+                     b->out_gxpos && b->out_gxmat && b->out_xpos && b->out_xquat && b->rows,
+                 "rmbx_episode_trace: a chunk pointer is NULL");
+  RMBX_CHECK_ARG(b->stride >= 1, "rmbx_episode_trace: stride must be at least 1 (got %d)", b->stride);
+  RMBX_CHECK_ARG(b->capacity >= 1, "rmbx_episode_trace: capacity must be at least 1 (got %d)", b->capacity);
+  RMBX_CHECK_ARG(b->n_env >= 0 && b->n_episodes >= 0 && b->n_pre >= 0,
+                 "rmbx_episode_trace: negative n_env / n_episodes / n_pre");
+  RMBX_CHECK_ARG(b->nq > 0 && b->nv > 0 && b->nu > 0 && b->ngeom > 0 && b->nbody > 0,
+                 "rmbx_episode_trace: nq, nv, nu, ngeom and nbody must be positive");
+  RMBX_CHECK_ARG(b->ctrl_stride >= b->nu, "rmbx_episode_trace: ctrl_stride is smaller than nu");
+  if (b->n_env == 0) return RMBX_OK;
+  hipLaunchKernelGGL(episode_trace_index_kernel, dim3(1), dim3(kChunk), 0, stream_of(stream), *b);
+  RMBX_CHECK_LAUNCH();
+  hipLaunchKernelGGL(episode_trace_copy_kernel, dim3(b->n_env, kTraceArrays), dim3(kTraceThreads), 0,
+                     stream_of(stream), *b);
   RMBX_CHECK_LAUNCH();
   return RMBX_OK;
 }

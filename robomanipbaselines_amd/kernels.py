@@ -441,6 +441,115 @@ class EpisodeStream:
         return self.results.cpu().numpy().view(N.EPISODE_DTYPE).reshape(-1)
 
 
+# the arrays of a trace chunk: name -> (dtype, per-row shape as a function of the dimensions)
+TRACE_FIELDS = (
+    ("episode", torch.int32, lambda d: ()), ("slot", torch.int32, lambda d: ()), ("step", torch.int32, lambda d: ()),
+    ("phase", torch.int32, lambda d: ()), ("rollout_time_idx", torch.int32, lambda d: ()),
+    ("flags", torch.uint8, lambda d: ()), ("time", torch.float64, lambda d: ()), ("reward", torch.float64, lambda d: ()),
+    ("ctrl", torch.float64, lambda d: (d["nu"],)), ("qpos", torch.float64, lambda d: (d["nq"],)),
+    ("qvel", torch.float64, lambda d: (d["nv"],)), ("gxpos", torch.float64, lambda d: (d["ngeom"], 3)),
+    ("gxmat", torch.float64, lambda d: (d["ngeom"], 9)), ("xpos", torch.float64, lambda d: (d["nbody"], 3)),
+    ("xquat", torch.float64, lambda d: (d["nbody"], 4)),
+)
+TRACE_POLL_STEPS = 16  # env-steps between two flushes of the chunk: its capacity is this many steps of rows
+
+
+class EpisodeTrace:
+    """The device chunk and per-slot state of rmbx_episode_trace, shape-checked once.  `engine`
+    needs the PhysicsEngine tensors (time, _ctrl_store, qpos, qvel, gxpos, gxmat, xpos, xquat and
+    nq / nv / nu / ngeom / nbody).  slot_episode i32 [n] (None: slot e holds episode episode_base +
+    e), select u8 [n_episodes] (None: every episode), bad_resets i32 [n] (None: no row is flagged
+    as closed by a bad state), n_pre the phase index of RolloutPhase (sched_active's).  capacity defaults to the rows of one poll period, 16 n, so the
+    overflow flag can only mean that a flush was skipped; flush() raises on it."""
+
+    def __init__(self, sched, engine, n_episodes, n_pre, episode_base=0, slot_episode=None, select=None, stride=1,
+                 bad_resets=None, capacity=None):
+        n, dev = sched.shape[0], sched.device
+        dims = {k: int(getattr(engine, k)) for k in ("nq", "nv", "nu", "ngeom", "nbody")}
+        _chk(sched, torch.uint8, (n, N.SCHED_DTYPE.itemsize), "sched")
+        _chk(engine.time, torch.float64, (n,), "time")
+        _chk(engine._ctrl_store, torch.float64, None, "ctrl")
+        if engine._ctrl_store.dim() != 2 or engine._ctrl_store.shape[0] != n or engine._ctrl_store.shape[1] < dims["nu"]:
+            raise ValueError("ctrl must be [n, >= nu]")
+        _chk(engine.qpos, torch.float64, (n, dims["nq"]), "qpos")
+        _chk(engine.qvel, torch.float64, (n, dims["nv"]), "qvel")
+        _chk(engine.gxpos, torch.float64, (n, dims["ngeom"], 3), "gxpos")
+        _chk(engine.gxmat, torch.float64, (n, dims["ngeom"], 9), "gxmat")
+        _chk(engine.xpos, torch.float64, (n, dims["nbody"], 3), "xpos")
+        _chk(engine.xquat, torch.float64, (n, dims["nbody"], 4), "xquat")
+        if slot_episode is not None:
+            _chk(slot_episode, torch.int32, (n,), "slot_episode")
+        if select is not None:
+            _chk(select, torch.uint8, (int(n_episodes),), "select")
+        if bad_resets is not None:
+            _chk(bad_resets, torch.int32, (n,), "bad_resets")
+        if min(dims.values()) < 1:
+            raise ValueError(f"the trace needs positive dimensions, got {dims}")
+        if int(stride) < 1:
+            raise ValueError(f"stride must be at least 1, got {stride}")
+        capacity = TRACE_POLL_STEPS * n if capacity is None else int(capacity)
+        if capacity < 1:
+            raise ValueError(f"capacity must be at least 1, got {capacity}")
+        self.n, self.dims, self.capacity, self.stride = n, dims, capacity, int(stride)
+        self.sched, self.engine = sched, engine
+        self.slot_episode, self.select, self.bad_resets = slot_episode, select, bad_resets
+        self.trace_episode = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        self.trace_step = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.slot_row = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        self.rows = torch.zeros(2, dtype=torch.int32, device=dev)  # {rows used, overflow}
+        self.chunk = {name: torch.zeros((capacity,) + shape(dims), dtype=dt, device=dev)
+                      for name, dt, shape in TRACE_FIELDS}
+        b = N.TraceBuffers()
+        for name, t in (("sched", sched), ("slot_episode", slot_episode), ("select", select), ("bad_resets", bad_resets),
+                        ("time", engine.time), ("ctrl", engine._ctrl_store), ("qpos", engine.qpos),
+                        ("qvel", engine.qvel), ("gxpos", engine.gxpos), ("gxmat", engine.gxmat), ("xpos", engine.xpos),
+                        ("xquat", engine.xquat), ("trace_episode", self.trace_episode),
+                        ("trace_step", self.trace_step), ("slot_row", self.slot_row), ("rows", self.rows)):
+            setattr(b, name, N.ptr(t))
+        for name, _, _ in TRACE_FIELDS:
+            setattr(b, "out_" + name, N.ptr(self.chunk[name]))
+        b.n_env, b.n_episodes, b.episode_base = n, int(n_episodes), int(episode_base)
+        b.stride, b.capacity, b.n_pre = self.stride, capacity, int(n_pre)
+        b.nq, b.nv, b.nu, b.ctrl_stride = dims["nq"], dims["nv"], dims["nu"], engine._ctrl_store.shape[1]
+        b.ngeom, b.nbody = dims["ngeom"], dims["nbody"]
+        self._bufs = b
+
+    @property
+    def row_bytes(self):
+        """Bytes of one row over all arrays of the chunk."""
+        return sum(t[0].numel() * t.element_size() for t in self.chunk.values())
+
+    def record(self, stepped, reward):
+        """One env-step (rmbx_episode_trace): stepped u8 [n] is the mask the step ran under (None:
+        all), reward f64 [n] the step's reward.  No host synchronisation."""
+        import ctypes
+
+        if stepped is not None:
+            _chk(stepped, torch.uint8, (self.n,), "stepped")
+        _chk(reward, torch.float64, (self.n,), "reward")
+        self._bufs.stepped, self._bufs.reward = N.ptr(stepped), N.ptr(reward)
+        N.call("rmbx_episode_trace", ctypes.byref(self._bufs), N.stream_ptr())
+
+    def flush(self):
+        """The used rows as pinned host arrays {name: numpy [rows, ...]} (None when there are none),
+        and the chunk empty again.  One host synchronisation.  RuntimeError if the chunk overflowed
+        since the last flush: rows were lost."""
+        used, overflow = (int(x) for x in self.rows.cpu())
+        if overflow:
+            raise RuntimeError(f"the episode trace chunk overflowed ({self.capacity} rows): rows were dropped "
+                               "because a flush was skipped")
+        if used == 0:
+            return None
+        host = {}
+        for name, t in self.chunk.items():
+            h = torch.empty((used,) + tuple(t.shape[1:]), dtype=t.dtype, pin_memory=True)
+            h.copy_(t[:used], non_blocking=True)
+            host[name] = h
+        self.rows.zero_()
+        torch.cuda.current_stream().synchronize()
+        return {name: h.numpy() for name, h in host.items()}
+
+
 # ------------------------------------------------------------------------------------------
 # Vision-trunk epilogues (NHWC = torch channels_last)
 # ------------------------------------------------------------------------------------------
