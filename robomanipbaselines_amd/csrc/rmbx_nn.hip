@@ -218,7 +218,8 @@ extern "C" int rmbx_nhwc_bias_relu_maxpool(const void* x, const float* bias, voi
 
 // ---------------------------------------------------------------------------------------------
 // Residual add + LayerNorm of the ACT transformer (post-norm layers: norm(x + sublayer(x))),
-// one wavefront per token row, the row held in registers (D <= 1024): s = rnd(x + r) in the
+// one wavefront per token row, the row held in registers (D <= 2048: up to 8 float4 / 4 bf16x8
+// per lane, the lanes past D / VEC idle in the last pass): s = rnd(x + r) in the
 // storage dtype (the unfused add), mean and variance in f32 over s (two passes over registers),
 // y = rnd((s - mean) * rstd * w + b).  Replaces the add + nn.LayerNorm pair of
 // EncoderLayer/DecoderLayer (ACT transformer.py, third_party/act [absent]).

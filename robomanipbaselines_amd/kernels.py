@@ -680,7 +680,8 @@ def pointcloud_fps(depth, rgb, fovy_deg, num_points, stats, min_bound=None, max_
 
 def add_layernorm(x, r, weight, bias, eps=1e-5, out=None):
     """LayerNorm(rnd(x + r)) over the last dim (rmbx_add_layernorm); x, r [..., D] contiguous
-    bf16/f32 device tensors (r may be None), weight/bias f32 [D]."""
+    bf16/f32 device tensors (r may be None), weight/bias f32 [D]; D a multiple of 4 (f32) / 8 (bf16),
+    at most 2048.  out: a contiguous tensor of x's shape, dtype and device (x itself: in place)."""
     if x.dtype not in _NN_DTYPES or not x.is_cuda or not x.is_contiguous():
         raise ValueError("x must be a contiguous bf16/f32 device tensor")
     D = x.shape[-1]
@@ -690,6 +691,10 @@ def add_layernorm(x, r, weight, bias, eps=1e-5, out=None):
     _chk(bias, torch.float32, (D,), "bias")
     if out is None:
         out = torch.empty_like(x)
+    else:
+        _chk(out, x.dtype, x.shape, "out")
+        if out.device != x.device:
+            raise ValueError(f"out must be on {x.device} (got {out.device})")
     N.call("rmbx_add_layernorm", N.ptr(x), N.ptr(r), N.ptr(weight), N.ptr(bias), N.ptr(out), x.numel() // D, D,
            float(eps), _NN_DTYPES[x.dtype], N.stream_ptr())
     return out
