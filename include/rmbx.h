@@ -912,6 +912,37 @@ int rmbx_ddim_step(const float* model_output, const float* sample, float* prev_s
                    const float* coeffs, int eps_mode, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Per-episode sampler noise (opt-in, --sampler_noise episode): the initial trajectory and the DDPM
+ * variance noise of the diffusion samplers from a counter-based generator keyed per episode, as
+ * the reset noise is, in place of the reference's draws from the global torch.randn stream.
+ *
+ * The rule.  Noise element i of a row of length L = horizon * action_dim is a pure function of
+ * (seed, episode, draw, plane, i):
+ *   generator  Philox4x32-10 (Random123): multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants
+ *              0x9E3779B9, 0xBB67AE85
+ *   key        (seed & 0xffffffff, seed >> 32), seed the unsigned 64-bit --seed
+ *   counter    (j, plane, draw, episode) as four uint32; j = i / 4 is the block within the row;
+ *              episode is the int32 bit pattern (a retired slot's -1 is 0xffffffff, no special case)
+ *   plane      0 = the initial trajectory x0; 1 + k = the k-th variance noise (the k-th step with
+ *              t > 0 of the sampling loop)
+ *   draw       the number of sampler calls the episode has made before this one
+ *   uniforms   the four words w0..w3 of block j give elements 4j .. 4j+3; for a pair (wa, wb):
+ *              u1 = ((wa >> 9) + 0.5) * 2^-23, u2 = ((wb >> 9) + 0.5) * 2^-23, both exact in f32
+ *              and inside the open interval (0, 1)
+ *   normals    r = sqrtf(-2 * logf(u1)); (z_even, z_odd) = r * (cospi(2 * u2), sinpi(2 * u2));
+ *              (w0, w1) gives elements 4j and 4j+1, (w2, w3) gives 4j+2 and 4j+3.  The accurate
+ *              logf / sqrtf / sincospif; sincospif is handed 2 * u2, which is exact
+ *   bound      |z| <= sqrt(-2 ln 2^-24) = 5.77
+ *
+ * episode, draw i32 [n] device.  out [nplane][n][L] f32 (kind 0: normals) or [nplane][n][4 *
+ * ceil(L / 4)] u32 (kind 1: the raw words), planes plane0 .. plane0 + nplane - 1; 4-byte aligned.
+ * Nothing is written past the end of out.  n, L, nplane >= 1, plane0 >= 0, n * ceil(L / 4) < 2^31
+ * (RMBX_ERR_ARG otherwise, before any launch).
+ * ------------------------------------------------------------------------------------------- */
+int rmbx_philox_normal(uint64_t seed, const int32_t* episode, const int32_t* draw, int plane0, int nplane,
+                       void* out, int n, int L, int kind, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Policy-input image preprocessing, batched over envs.
  * rmbx_resize_crop_u8: src u8 [n][H][W][C] (renderer frames) -> dst [n][C][ch][cw] (f32 dtype 0 /
  * bf16 dtype 1) = (v * (1/255)) * a + b, v = cv2.resize(src, (rw, rh), INTER_LINEAR)[y0+y, x0+x];

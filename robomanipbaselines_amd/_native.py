@@ -117,6 +117,7 @@ SIGNATURES = {
     "rmbx_add_layernorm_pos": (_c_int, [_c_p] * 6 + [_c_int, _c_p, _c_int, _c_int, ctypes.c_float, _c_int, _c_p]),
     "rmbx_ddpm_step": (_c_int, [_c_p] * 4 + [_c_sz, _c_p, _c_p]),
     "rmbx_ddim_step": (_c_int, [_c_p] * 3 + [_c_sz, _c_p, _c_int, _c_p]),
+    "rmbx_philox_normal": (_c_int, [ctypes.c_uint64, _c_p, _c_p, _c_int, _c_int, _c_p, _c_int, _c_int, _c_int, _c_p]),
     "rmbx_resize_crop_u8": (_c_int, [_c_p] + [_c_int] * 10 + [ctypes.c_float, ctypes.c_float, _c_p, _c_int, _c_p]),
     "rmbx_resize_f32": (_c_int, [_c_p, _c_p] + [_c_int] * 5 + [_c_p]),
     "rmbx_pointcloud_fps": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_int, _c_d, _c_p, _c_p, _c_int, _c_int,

@@ -392,6 +392,8 @@ class BatchedRolloutBase:
             "num_episodes": count, "num_slots": self.n, "trace_episodes": "all" if chosen is None else chosen,
             "max_duration": float(a.max_duration), "rank": rank, "world_size": world,
         }
+        if hasattr(a, "sampler_noise"):  # the diffusion policies: which noise a re-run must ask for
+            header["sampler_noise"] = str(a.sampler_noise)
         self._trace = TraceWriter(directory, header, trace)
         # the size the run can reach: an episode ends by max_duration + the post-success second
         dt = env.frame_skip * env.sim_timestep

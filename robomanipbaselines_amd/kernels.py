@@ -640,6 +640,65 @@ def resize_f32(src, size, out=None):
 
 
 # ------------------------------------------------------------------------------------------
+# Per-episode sampler noise (diffusion policies, --sampler_noise episode)
+# ------------------------------------------------------------------------------------------
+def philox_normal(seed, episode, draw, out, plane0=0, L=None, words=False):
+    """Fill `out` in place with the per-episode sampler noise of include/rmbx.h (rmbx_philox_normal):
+    row r of plane p is the Philox4x32-10 stream of (seed, episode[r], draw[r], plane0 + p).
+
+    episode, draw: i32 [n].  out: f32 [nplane, n, ...] standard normals, the row length L being the
+    product of the trailing dimensions (or `L`, which must then agree); with words=True the raw
+    generator words, i32 [nplane, n, 4 * ceil(L / 4)] (`L` required).  Shapes and dtypes are checked
+    before the device, so a wrong call fails the same way everywhere.  Returns out."""
+    seed = int(seed)
+    if not 0 <= seed < 2**64:
+        raise ValueError(f"seed must be an unsigned 64-bit value (got {seed})")
+    plane0 = int(plane0)
+    if plane0 < 0:
+        raise ValueError(f"plane0 must be non-negative (got {plane0})")
+    want = torch.int32 if words else torch.float32
+    for t, dt, name in ((episode, torch.int32, "episode"), (draw, torch.int32, "draw"), (out, want, "out")):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch.Tensor")
+        if t.dtype != dt:
+            raise ValueError(f"{name} must be {dt} (got {t.dtype})")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    if episode.dim() != 1 or episode.shape[0] < 1:
+        raise ValueError(f"episode must have shape [n], n >= 1 (got {tuple(episode.shape)})")
+    n = int(episode.shape[0])
+    if tuple(draw.shape) != (n,):
+        raise ValueError(f"draw must have shape {(n,)} (got {tuple(draw.shape)})")
+    if out.dim() < 3 or out.shape[0] < 1 or out.shape[1] != n:
+        raise ValueError(f"out must have shape [nplane, {n}, ...] (got {tuple(out.shape)})")
+    nplane = int(out.shape[0])
+    row = int(np.prod(out.shape[2:]))
+    if words:
+        if L is None or int(L) < 1:
+            raise ValueError("words=True needs the row length L >= 1")
+        L = int(L)
+        if out.dim() != 3 or row != 4 * ((L + 3) // 4):
+            raise ValueError(f"out must have shape {(nplane, n, 4 * ((L + 3) // 4))} for L = {L} "
+                             f"(got {tuple(out.shape)})")
+    else:
+        if row < 1:
+            raise ValueError(f"out rows must not be empty (got {tuple(out.shape)})")
+        if L is not None and int(L) != row:
+            raise ValueError(f"L = {L} does not match the rows of out {tuple(out.shape)}")
+        L = row
+    if plane0 + nplane > 2**31 - 1:
+        raise ValueError(f"plane0 + nplane exceeds 2^31 - 1 (got {plane0} + {nplane})")
+    for t, name in ((episode, "episode"), (draw, "draw"), (out, "out")):
+        if not t.is_cuda:
+            raise ValueError(f"{name} must be a device tensor (got {t.device})")
+        if t.device != out.device:
+            raise ValueError(f"{name} is on {t.device}, out on {out.device}")
+    N.call("rmbx_philox_normal", seed, N.ptr(episode), N.ptr(draw), plane0, nplane, N.ptr(out), n, L,
+           1 if words else 0, N.stream_ptr())
+    return out
+
+
+# ------------------------------------------------------------------------------------------
 # Point-cloud observation (3D diffusion policy)
 # ------------------------------------------------------------------------------------------
 def focal_scaling(fovy_deg, height):

@@ -13,7 +13,9 @@ already-normalised data, RolloutDiffusionPolicy.py:89-105).  Parity vs upstream:
 
 The denoising loop (100 UNet evaluations + the rmbx_ddpm_step kernel per step) is captured once
 into a HIP graph (torch.cuda.CUDAGraph) per batch size and replayed on every inference; the
-initial trajectory and the per-step noise are drawn into static buffers before each replay.
+initial trajectory and the per-step noise are drawn into static buffers before each replay:
+torch.randn draws for the whole batch by default, or, given a noise source, the per-episode Philox
+noise of rmbx_philox_normal written into them in place.
 """
 
 import numpy as np
@@ -210,43 +212,82 @@ class DiffusionPolicyModel(nn.Module):
     # tests/test_diffusion_policy_gpu.py): no batch cap.
     graph_max_batch = None
 
-    def conditional_sample(self, global_cond, use_graph=True, x0=None, noise=None):
+    # Optional callable(x0 [B, horizon, A], noise [n_noise, B, horizon, A] or None), called after a
+    # noise source has filled them and before the loop reads them (tests and diagnostics hash them)
+    noise_hook = None
+
+    def _fill_noise(self, noise_source, planes):
+        """planes [1 + n_noise, B, horizon, A] f32 <- the per-episode noise of noise_source =
+        (seed, episode [B] i32, draw [B] i32): plane 0 the initial trajectory, 1 + k the k-th
+        variance noise (rmbx_philox_normal, one launch on the current stream).  Returns (x0, noise)."""
+        from ... import kernels as K
+
+        seed, episode, draw = noise_source
+        K.philox_normal(seed, episode, draw, planes, plane0=0)
+        x0, noise = planes[0], (planes[1:] if planes.shape[0] > 1 else None)
+        if self.noise_hook is not None:
+            self.noise_hook(x0, noise)
+        return x0, noise
+
+    def conditional_sample(self, global_cond, use_graph=True, x0=None, noise=None, noise_source=None):
         """Sample [B, horizon, A].  x0 (initial trajectory) and noise ([n_noise, B, horizon, A])
-        default to fresh torch.randn draws (the reference draws them with torch.randn too)."""
+        default to fresh torch.randn draws (the reference draws them with torch.randn too).
+        With noise_source = (seed, episode [B] i32, draw [B] i32) they are instead the per-episode
+        Philox noise of include/rmbx.h, written in place by one kernel (on the graph path straight
+        into the static buffers, before the replay and outside the captured graph): row b is a
+        function of (seed, episode[b], draw[b]) alone, whatever the batch around it."""
         B = global_cond.shape[0]
         dev = global_cond.device
         if getattr(self, "_tsteps", None) is None or self._tsteps[0].device != dev:
             self._tsteps = [torch.tensor(int(t), device=dev) for t in self.sampler.timesteps]
         shape = (B, self.horizon, self.action_dim)
         nn_ = self._n_noise()
-        if x0 is None:
-            x0 = torch.randn(shape, device=dev)
-        if noise is None:
-            noise = torch.randn((nn_,) + shape, device=dev) if nn_ else None
+        if noise_source is not None:
+            if x0 is not None or noise is not None:
+                raise ValueError("noise_source cannot be combined with explicit x0 / noise")
+        else:
+            if x0 is None:
+                x0 = torch.randn(shape, device=dev)
+            if noise is None:
+                noise = torch.randn((nn_,) + shape, device=dev) if nn_ else None
         if not use_graph or dev.type != "cuda" or (self.graph_max_batch is not None and B > self.graph_max_batch):
+            if noise_source is not None:
+                x0, noise = self._fill_noise(noise_source, torch.empty((1 + nn_,) + shape, device=dev))
             return self._sample_loop(global_cond, x0.contiguous(), noise)
         key = (B, self.dtype)
+        filled = False
         if key not in self._graphs:
             gc = torch.zeros_like(global_cond)
-            xb = torch.zeros(shape, device=dev)
-            nb = torch.zeros((nn_,) + shape, device=dev) if nn_ else None
+            # one allocation, so that a noise source fills x0 and the noise planes in one launch
+            planes = torch.zeros((1 + nn_,) + shape, device=dev)
+            xb, nb = planes[0], (planes[1:] if nn_ else None)
+            if noise_source is not None:
+                # the warm-up below reads the static buffers themselves and the replay reuses them
+                # without a refill: sound because sampler.step never writes its sample or noise
+                # argument (it returns a new tensor), so the warm-up leaves them as filled
+                x0, noise = self._fill_noise(noise_source, planes)
+                filled = True
             self._sample_loop(global_cond, x0.contiguous(), noise)  # warm-up: solver selection outside capture
             torch.cuda.synchronize(dev)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 out = self._sample_loop(gc, xb, nb)
-            self._graphs[key] = (g, gc, xb, nb, out)
-        g, gc, xb, nb, out = self._graphs[key]
+            self._graphs[key] = (g, gc, xb, nb, out, planes)
+        g, gc, xb, nb, out, planes = self._graphs[key]
         gc.copy_(global_cond)
-        xb.copy_(x0)
-        if nb is not None:
-            nb.copy_(noise)
+        if noise_source is not None:
+            if not filled:
+                self._fill_noise(noise_source, planes)
+        else:
+            xb.copy_(x0)
+            if nb is not None:
+                nb.copy_(noise)
         g.replay()
         return out
 
     @torch.no_grad()
-    def predict_action(self, state, images, use_graph=True, x0=None, noise=None):
+    def predict_action(self, state, images, use_graph=True, x0=None, noise=None, noise_source=None):
         gcond = self.encode_obs(state, images)
-        traj = self.conditional_sample(gcond, use_graph, x0, noise)
+        traj = self.conditional_sample(gcond, use_graph, x0, noise, noise_source)
         start = self.n_obs_steps - 1
         return traj[:, start:start + self.n_action_steps]

@@ -8,6 +8,9 @@ reference for n_env envs.
 * infer_policy (:66-87): when the action buffer is empty, predict_action (obs encoder + 100-step
   DDPM loop, HIP-graph captured) -> n_action_steps actions; each call pops one and
   denormalises it (rmbx_act_ensemble, no-ensemble mode, bit-exact f64).
+* --sampler_noise episode (opt-in): the sampler's noise from the Philox stream of (seed, global
+  episode index, inference count of the episode) instead of torch.randn draws for the batch, so an
+  episode does not depend on the layout it runs in.
 Training-side defaults (TrainDiffusionPolicy.py:26-84): limits normalisation to [-1, 1],
 horizon 16, n_obs_steps 2, n_action_steps 8, image_size 320x240, crop 288x216.
 """
@@ -33,6 +36,12 @@ class RolloutDiffusionPolicy(BatchedRolloutBase):
 
     def set_additional_args(self, parser):
         parser.add_argument("--no_graph", action="store_true", help="run the denoising loop eagerly")
+        parser.add_argument("--sampler_noise", choices=["batch", "episode"], default="batch",
+                            help="where the sampler's initial trajectory and variance noise come from. batch "
+                                 "(default): torch.randn draws for the whole batch, as the reference draws them; a "
+                                 "row's noise depends on the batch layout. episode: a Philox stream keyed by "
+                                 "(--seed, global episode index, inference count of the episode), the same in every "
+                                 "layout (slot count, slot, --env_offset / --episode_offset, --num_gpus)")
 
     def setup_model_meta_info(self):
         super().setup_model_meta_info()
@@ -64,16 +73,24 @@ class RolloutDiffusionPolicy(BatchedRolloutBase):
                                               and os.environ.get("RMBX_DP_DETERMINISTIC", "1") != "0")
         self.policy = self.policy.eval().requires_grad_(False).to(device=self.device, dtype=self.policy_dtype)
         self.policy.obs_nets = self.policy.obs_nets.to(memory_format=torch.channels_last)
+        self._print_sampler_noise()
+
+    def _print_sampler_noise(self):
+        print(f"[{self.__class__.__name__}] Sampler noise: {getattr(self.args, 'sampler_noise', 'batch')}", flush=True)
 
     @property
     def infer_period_calls(self):
         return self.n_action_steps
 
     def reset_policy_state(self, mask):
-        """The sampler draws its noise per call for all rows, so a streaming run's episodes are
-        reproducible for a fixed slot count, not across slot counts."""
+        """--sampler_noise batch: the sampler draws its noise per call for all rows, so a streaming
+        run's episodes are reproducible for a fixed slot count, not across slot counts.  episode:
+        the rows of `mask` begin a new noise stream (their draw counter returns to 0), so an
+        episode's noise is the same in every layout."""
         self.ens.reset(mask)
         self._reset_obs_history(mask)
+        if getattr(self, "_draw", None) is not None:
+            self._draw.masked_fill_(mask.bool(), 0)
 
     def reset_variables(self):
         self.ens = K.ActEnsembleState(self.n, self.n_action_steps, self.action_dim, self.model_meta_info["action"],
@@ -82,6 +99,30 @@ class RolloutDiffusionPolicy(BatchedRolloutBase):
         self.images_buf = None
         self._calls = 0
         self._first_obs = None
+        # --sampler_noise episode: the draw counter of every row (sampler calls its episode has made)
+        # and, for a lockstep run, the rows' global episode indices (a streaming run reads the
+        # stream's slot -> episode map, which the device updates)
+        self._draw = self._lockstep_episode = None
+        if getattr(self.args, "sampler_noise", "batch") == "episode":
+            self._draw = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+            self._lockstep_episode = torch.arange(self.args.env_offset, self.args.env_offset + self.n,
+                                                  dtype=torch.int32, device=self.device)
+
+    def _noise_source(self):
+        """(seed, episode [n] i32, draw [n] i32) of the next sampler call, or None (--sampler_noise batch)."""
+        if self._draw is None:
+            return None
+        streaming = self.args.num_episodes is not None
+        episode = self.stream.slot_episode if streaming else self._lockstep_episode
+        return int(self.args.seed) & (2**64 - 1), episode, self._draw
+
+    def _predict(self, *obs):
+        """predict_action of a push step; afterwards every row has made one more sampler call."""
+        chunk = self.policy.predict_action(*obs, use_graph=not self.args.no_graph,
+                                           noise_source=self._noise_source()).float().contiguous()
+        if self._draw is not None:
+            self._draw += 1
+        return chunk
 
     def get_state(self):
         s = super().get_state()
@@ -116,7 +157,7 @@ class RolloutDiffusionPolicy(BatchedRolloutBase):
         if push:
             state = self.get_state()
             images = self.get_images(self.policy_dtype)
-            chunk = self.policy.predict_action(state, images, use_graph=not self.args.no_graph).float().contiguous()
+            chunk = self._predict(state, images)
             self._first_obs = None
         p = torch.full((self.n,), int(push), dtype=torch.uint8, device=self.device)
         self.policy_action = self.ens(chunk, push=p)

@@ -56,6 +56,7 @@ class RolloutDiffusionPolicy3d(RolloutDiffusionPolicy):
         torch.backends.cudnn.benchmark = False
         torch.backends.cudnn.deterministic = True
         self.policy = self.policy.eval().requires_grad_(False).to(device=self.device, dtype=self.policy_dtype)
+        self._print_sampler_noise()
 
     def reset_variables(self):
         super().reset_variables()
@@ -86,7 +87,7 @@ class RolloutDiffusionPolicy3d(RolloutDiffusionPolicy):
         if push:
             state = self.get_state()
             pc = self.get_pointcloud()
-            chunk = self.policy.predict_action(state, pc, use_graph=not self.args.no_graph).float().contiguous()
+            chunk = self._predict(state, pc)
             self._first_obs = None
         p = torch.full((self.n,), int(push), dtype=torch.uint8, device=self.device)
         self.policy_action = self.ens(chunk, push=p)

@@ -48,7 +48,7 @@ POLICIES = {
 }
 
 
-def main():
+def parse_args(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("policy", choices=sorted(POLICIES))
     p.add_argument("--num_envs", type=int, default=1024)
@@ -60,9 +60,26 @@ def main():
     p.add_argument("--shadows", choices=["off", "scene"], default="off", help="the renderer's shadows (Rollout.py --shadows)")
     p.add_argument("--offsamples", choices=["1", "4", "scene"], default="1",
                    help="samples per pixel of the camera images (Rollout.py --offsamples)")
-    a = p.parse_args()
+    p.add_argument("--sampler_noise", choices=["batch", "episode"], default=None,
+                   help="the diffusion policies' noise source (Rollout.py --sampler_noise; default: batch)")
+    a = p.parse_args(argv)
+    if a.sampler_noise is not None and not a.policy.startswith("DiffusionPolicy"):
+        p.error("--sampler_noise is a flag of the diffusion policies")
     a.env = a.env or DEFAULT_ENV[a.policy]
     a.precision = a.precision or ("fp32" if a.policy == "Sarnn" else "bf16")
+    return a
+
+
+def rollout_argv(a):
+    """The Rollout command line of the parsed benchmark arguments."""
+    return (["--num_envs", str(a.num_envs), "--device", "cuda:0", "--world_idx_list", *[str(i) for i in range(6)],
+             "--world_random_scale", "0.01", "0.01", "0.0", "--seed", "0", "--precision", a.precision,
+             "--shadows", a.shadows, "--offsamples", a.offsamples] + (["--tactile"] if a.tactile else [])
+            + (["--sampler_noise", a.sampler_noise] if a.sampler_noise else []))
+
+
+def main():
+    a = parse_args()
     import importlib
 
     mod, cls = POLICIES[a.policy]
@@ -71,9 +88,7 @@ def main():
     class Rollout(ENVS[a.env], Pol):
         pass
 
-    argv = ["--num_envs", str(a.num_envs), "--device", "cuda:0", "--world_idx_list", *[str(i) for i in range(6)],
-            "--world_random_scale", "0.01", "0.01", "0.0", "--seed", "0", "--precision", a.precision,
-            "--shadows", a.shadows, "--offsamples", a.offsamples] + (["--tactile"] if a.tactile else [])
+    argv = rollout_argv(a)
     t_start = time.time()
 
     def log(msg):
@@ -121,7 +136,7 @@ def main():
                       "infer_ms_per_call": round(float(np.mean(inf)), 3) if inf else None,
                       "scene": a.env + (" minus YCB_sim" if a.env == "MujocoUR5ePick" else ""),
                       "tactile": "synthetic, every env-step" if a.tactile else None, "shadows": a.shadows,
-                      "offsamples": a.offsamples,
+                      "offsamples": a.offsamples, "sampler_noise": a.sampler_noise,
                       "data": "synthetic (random-init weights)"}), flush=True)
 
 
