@@ -352,6 +352,90 @@ typedef struct rmbx_trace_buffers {
 
 int rmbx_episode_trace(const rmbx_trace_buffers* bufs, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Per-episode rollout metrics (--episode_metrics): how fast, how hard and how smoothly the policy
+ * drove each episode, accumulated on the device into one row per episode.
+ * Called once per env-step, after the physics step (and the env's bad-state bookkeeping) and
+ * BEFORE rmbx_sched_update of that step: the schedule it reads is the one the step was taken
+ * under.  One thread per slot; a given episode is summed by one thread in step order, f64, no
+ * contraction, so its row does not depend on slot count, slot index or launch geometry.
+ *
+ * Slot rule, every slot s on its own:
+ *  1. The slot is counted iff  active[s] != 0 (active NULL: every slot),  sched[s].phase == n_pre
+ *     (RolloutPhase only: the scripted pre-motion phases are not the policy's),  sched[s].done == 0
+ *     and its episode is in the table:  ep = slot_episode[s] (slot_episode NULL: episode_base + s),
+ *     0 <= ep - episode_base < n_episodes.  A slot that is not counted reads and writes nothing
+ *     else.
+ *  2. row = table[ep - episode_base], read-modify-write.  A row with steps == 0 is empty (the
+ *     caller zero-fills the table).
+ *  3. Divergence guard: bad_resets[s] > 0 (bad_resets NULL: never) -> nothing is accumulated;
+ *     flags |= 1 if the row is not empty; done.  (The engine rewound the state: a path step across
+ *     the jump means nothing.  Streaming closes such an episode with this step; in lockstep the
+ *     episode goes on and its metrics stop here.)
+ *  4. k = steps + 1, the index of this counted step within the episode, then with
+ *       f = sensordata[s][0:3], t = sensordata[s][3:6]     (sensordata [n_env][6])
+ *       q[j] = qpos[s][arm_qadr[j]], v[j] = qvel[s][arm_dof[j]], u[j] = ctrl[s][j]      (j < 6)
+ *       p    = the 3 doubles at ee_pos + s * ee_stride     (the end-effector point)
+ *     and the slot's history hist[s] = {p' (3), q' (6), u' (6), u'' (6)} = p, q, u of the
+ *     episode's previous counted step and u of the one before it:
+ *       k == 1: episode = ep
+ *       first_success_step = k        if it is 0 and reward[s] > 0
+ *       peak_force           = max(.., sqrt((f0*f0 + f1*f1) + f2*f2))
+ *       peak_torque          = max(.., sqrt((t0*t0 + t1*t1) + t2*t2))
+ *       peak_joint_speed     = max(.., |v[j]|)          for j = 0..5
+ *       peak_tracking_error  = max(.., |u[j] - q[j]|)   for j = 0..5
+ *       k >= 2: ee_path     += sqrt((dx*dx + dy*dy) + dz*dz),  d = p - p'
+ *       k >= 2: joint_path  += sum over j = 0..5 in order, from 0, of |q[j] - q'[j]|
+ *       k >= 3: cmd_roughness += sum over j = 0..5 in order, from 0, of d*d,
+ *                                 d = (u[j] - 2*u'[j]) + u''[j]
+ *       steps = k
+ *     The inner sum over j is formed first and then added to the running total.  max(cur, x) is
+ *     `x > cur ? x : cur` from cur = 0: a NaN never enters a peak.  Peaks are sampled at env-step
+ *     rate (the policy's own rate), not per substep.
+ *  5. History: k == 1 seeds p' = p, q' = q, u' = u'' = u; later steps set u'' = u', u' = u, p' = p,
+ *     q' = q.  Because an empty row re-seeds it, a recycled slot needs no reset call.
+ * Nothing but the rows of counted slots and their history is written; no atomics, no LDS.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct rmbx_episode_metrics_t {
+  int32_t episode;            /* global episode index, written on the first counted step */
+  int32_t steps;              /* K: counted env-steps (RolloutPhase steps before any bad-state reset) */
+  int32_t first_success_step; /* smallest k with reward > 0, 0 = never */
+  int32_t flags;              /* bit 0: stopped by the divergence guard */
+  double peak_force;          /* max |sensordata[0:3]| */
+  double peak_torque;         /* max |sensordata[3:6]| */
+  double peak_joint_speed;    /* max over the 6 arm joints of |qvel| */
+  double peak_tracking_error; /* max over the 6 arm joints of |ctrl - qpos| */
+  double ee_path;             /* length of the end-effector point's polyline */
+  double joint_path;          /* sum of the arm's L1 joint steps */
+  double cmd_roughness;       /* sum of the squared second differences of the arm command */
+} rmbx_episode_metrics_t;
+
+#define RMBX_METRICS_BAD_STATE 1
+#define RMBX_METRICS_HIST 21 /* doubles of history per slot: p'(3) q'(6) u'(6) u''(6) */
+
+/* Host struct of device pointers (read during the call only). */
+typedef struct rmbx_metrics_buffers {
+  const rmbx_sched_t* sched;      /* [n_env] */
+  const int32_t* slot_episode;    /* [n_env] or NULL */
+  const uint8_t* active;          /* [n_env] or NULL = all: the mask the step ran under */
+  const int32_t* bad_resets;      /* [n_env] or NULL */
+  const double* reward;           /* [n_env] */
+  const double* qpos;             /* [n_env][nq] */
+  const double* qvel;             /* [n_env][nv] */
+  const double* ctrl;             /* [n_env][ctrl_stride] */
+  const double* sensordata;       /* [n_env][6] */
+  const double* ee_pos;           /* 3 doubles per slot, ee_stride doubles apart */
+  rmbx_episode_metrics_t* table;  /* [n_episodes] */
+  double* hist;                   /* [n_env][RMBX_METRICS_HIST] kernel-owned */
+  int32_t n_env, n_episodes, episode_base;
+  int32_t n_pre;                  /* phase index of RolloutPhase, as rmbx_sched_active's */
+  int32_t nq, nv, nu, ctrl_stride, ee_stride;
+  int32_t arm_qadr[6];            /* qpos address of each arm joint */
+  int32_t arm_dof[6];             /* qvel address of each arm joint */
+} rmbx_metrics_buffers;
+
+int rmbx_episode_metrics(const rmbx_metrics_buffers* bufs, void* stream);
+
 
 /* ---------------------------------------------------------------------------------------------
  * Batched MuJoCo-subset physics engine (the env.step hot path).

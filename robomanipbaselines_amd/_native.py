@@ -45,6 +45,7 @@ SIGNATURES = {
     "rmbx_sched_close_bad": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_p]),
     "rmbx_episode_recycle": (_c_int, [_c_p, _c_p]),
     "rmbx_episode_trace": (_c_int, [_c_p, _c_p]),
+    "rmbx_episode_metrics": (_c_int, [_c_p, _c_p]),
     "rmbx_engine_create": (_c_int, [_c_p, _c_int, _c_p]),
     "rmbx_engine_destroy": (_c_int, [_c_p]),
     "rmbx_engine_workspace_bytes": (_c_int, [_c_p, _c_p]),
@@ -185,6 +186,16 @@ class TraceBuffers(ctypes.Structure):
                                                  "nq", "nv", "nu", "ctrl_stride", "ngeom", "nbody")])
 
 
+class MetricsBuffers(ctypes.Structure):
+    """ctypes mirror of rmbx_metrics_buffers (include/rmbx.h)."""
+
+    _fields_ = ([(n, _c_p) for n in ("sched", "slot_episode", "active", "bad_resets", "reward", "qpos", "qvel", "ctrl",
+                                     "sensordata", "ee_pos", "table", "hist")]
+                + [(n, ctypes.c_int32) for n in ("n_env", "n_episodes", "episode_base", "n_pre", "nq", "nv", "nu",
+                                                 "ctrl_stride", "ee_stride")]
+                + [("arm_qadr", ctypes.c_int32 * 6), ("arm_dof", ctypes.c_int32 * 6)])
+
+
 # flags of a trace row (include/rmbx.h RMBX_TRACE_*)
 TRACE_DONE, TRACE_SUCCESS, TRACE_BAD_STATE = 1, 2, 4
 
@@ -222,6 +233,26 @@ EPISODE_DTYPE = np.dtype(
     ]
 )
 assert EPISODE_DTYPE.itemsize == 40
+
+# numpy mirror of rmbx_episode_metrics_t (include/rmbx.h)
+METRICS_DTYPE = np.dtype(
+    [
+        ("episode", np.int32),
+        ("steps", np.int32),
+        ("first_success_step", np.int32),
+        ("flags", np.int32),
+        ("peak_force", np.float64),
+        ("peak_torque", np.float64),
+        ("peak_joint_speed", np.float64),
+        ("peak_tracking_error", np.float64),
+        ("ee_path", np.float64),
+        ("joint_path", np.float64),
+        ("cmd_roughness", np.float64),
+    ]
+)
+assert METRICS_DTYPE.itemsize == 72
+METRICS_BAD_STATE = 1  # include/rmbx.h RMBX_METRICS_BAD_STATE
+METRICS_HIST = 21  # include/rmbx.h RMBX_METRICS_HIST
 
 _lib = None
 

@@ -33,6 +33,7 @@ import torch
 import yaml
 
 from .. import kernels as K
+from ..common import episode_metrics as EM
 from ..common.data_key import DataKey, action_key_codes, state_key_codes
 from ..common.data_utils import make_meta_info
 from ..common.episode_trace import TraceWriter, parse_episodes, row_bytes, select_mask
@@ -74,6 +75,7 @@ class BatchedRolloutBase:
         self._active = None  # optional caller override of the per-env step mask
         self.phase_timer = None  # optional PhaseTimer (common/phase_timer.py): bench.py's per-phase split
         self._trace = None  # the TraceWriter of a run with --trace_dir
+        self._metrics = None  # the kernels.EpisodeMetrics accumulator of a run with --episode_metrics
 
     def attach_phase_timer(self, timer):
         """Record HIP events at the policy / render / physics / glue boundaries of every env-step
@@ -156,6 +158,11 @@ class BatchedRolloutBase:
         parser.add_argument("--trace_stride", type=int, default=1,
                             help="with --trace_dir: keep every K-th env-step of an episode and its last step; "
                                  "K = --skip keeps the steps whose frames the policy read")
+        parser.add_argument("--episode_metrics", action="store_true",
+                            help="accumulate per-episode metrics of the RolloutPhase on the device (steps to first "
+                                 "success, peak wrist force / torque, peak joint speed and tracking error, gripper and "
+                                 "joint path lengths, command roughness): a `metrics` key in the result file and a "
+                                 "summary with the success rate's Wilson interval after the statistics")
         if self.require_task_desc:
             parser.add_argument("--task_desc", type=str, required=True)
         self.set_additional_args(parser)
@@ -359,6 +366,51 @@ class BatchedRolloutBase:
         self.reset_variables()
         if getattr(self.args, "trace_dir", None) and self.args.num_episodes is None:
             self._trace_begin()
+        if getattr(self.args, "episode_metrics", False) and self.args.num_episodes is None:
+            self._metrics_begin()
+
+    # -- per-episode metrics (--episode_metrics) --------------------------------------------------
+    def _metrics_begin(self):
+        """Allocate the device metrics table of this run.  Lockstep: env e is episode env_offset + e;
+        streaming: one row per episode of the queue, addressed through the stream's slot -> episode
+        map."""
+        a, env = self.args, self.env
+        streaming = a.num_episodes is not None
+        self._metrics = K.EpisodeMetrics(
+            self.sched, env.engine, len(self.pre_durations), int(a.num_episodes) if streaming else self.n,
+            episode_base=int(a.episode_offset) if streaming else int(a.env_offset),
+            slot_episode=self.stream.slot_episode if streaming else None, bad_resets=env.bad_resets,
+            arm_qadr=env._arm_qadr.tolist(), arm_dof=env._arm_dadr.tolist())
+
+    def _metrics_finish(self, world_idx):
+        """Read the table (the one device read) and, under --num_gpus, all-gather the ranks' rows into
+        global episode order: self.episode_metrics (_native.METRICS_DTYPE).  Every rank calls it."""
+        table, widx = self._metrics.table(), np.asarray(world_idx, np.int64)
+        rank, world = self._dist_world()
+        if world > 1:
+            import torch.distributed as dist
+
+            from ..distributed import gather_table
+
+            dev = self.device if dist.get_backend() == "nccl" else "cpu"
+            table, widx = EM.columns_to_table(gather_table(EM.table_to_columns(table, widx), dev))
+        self.episode_metrics, self._metrics_world = table, widx
+
+    def _append_metrics_result(self):
+        """result["metrics"]: per-episode lists parallel to result["success"] (which a second run of
+        the same object extends, so these are extended too)."""
+        new = EM.metrics_result(self.episode_metrics, self._step_seconds())
+        cur = self.result.setdefault("metrics", {k: [] for k in new})
+        for k, v in new.items():
+            cur[k].extend(v)
+
+    def _step_seconds(self):
+        return self.env.frame_skip * self.env.sim_timestep
+
+    def _print_metrics(self, success):
+        for line in EM.summary_lines(EM.summarize(self.episode_metrics, success, self._metrics_world,
+                                                  self._step_seconds())):
+            print(line, flush=True)
 
     # -- episode trace (--trace_dir) -------------------------------------------------------------
     def _trace_begin(self):
@@ -496,6 +548,8 @@ class BatchedRolloutBase:
         self.obs, self.reward, _, _, self.info = self.env.step(self.env_action(), active=active)
         for _ in range(self.env.frame_skip):
             self.host_time += self.env.sim_timestep
+        if getattr(self, "_metrics", None) is not None:
+            self._metrics.step(active, self.reward)
         K.sched_update(self.sched, self.env.get_time(), self.reward, self._pre, self.args.max_duration)
         if getattr(self, "_trace", None) is not None:
             self._trace.step(active, self.reward)
@@ -573,6 +627,8 @@ class BatchedRolloutBase:
         self.episode_records = None
         if getattr(self.args, "trace_dir", None):
             self._trace_begin()
+        if getattr(self.args, "episode_metrics", False):
+            self._metrics_begin()
 
     def _reach_target(self, ph):
         """(R [n, 9], p [n, 3]) a reach phase would set now for every slot."""
@@ -615,6 +671,8 @@ class BatchedRolloutBase:
                              mask=in_rollout.to(torch.uint8))
         # 3. step + schedule
         self.obs, self.reward, _, _, self.info = self.env.step(self.env_action(), active=self._step_mask)
+        if getattr(self, "_metrics", None) is not None:
+            self._metrics.step(self._step_mask, self.reward)
         K.sched_update(self.sched, self.env.get_time(), self.reward, self._pre, self.args.max_duration)
         st.close_bad(n_pre)
         if getattr(self, "_trace", None) is not None:
@@ -698,12 +756,17 @@ class BatchedRolloutBase:
             dev = self.device if dist.get_backend() == "nccl" else "cpu"
             g = gather_results(pack_results(succ, rew, dur, v["rollout_time_idx"]), dev)
             succ, rew, dur = g[:, 0] != 0, g[:, 1], g[:, 2]
+        metrics = getattr(self, "_metrics", None) is not None
+        if metrics:
+            self._metrics_finish(self.world_idx)
         if rank == 0:
             for e in range(len(succ)):
                 print(f"Rollout result: {'success' if succ[e] else 'failure'}", flush=True)
                 self.result["success"].append(bool(succ[e]))
                 self.result["reward"].append(float(rew[e]))
                 self.result["duration"].append(float(dur[e]))
+            if metrics:
+                self._append_metrics_result()
         if self.args.save_last_image:
             self.save_rgb_images(v)
         if rank == 0 and self.args.result_filename is not None:
@@ -712,6 +775,8 @@ class BatchedRolloutBase:
                 yaml.dump(self.result, f)
         if rank == 0:
             self.print_statistics()
+            if metrics:
+                self._print_metrics(succ)
 
     def _finish_streaming(self):
         """finish() of a streaming run: one record per episode, in episode order.  An episode the
@@ -743,18 +808,25 @@ class BatchedRolloutBase:
             rec["success"], rec["reward"], rec["duration"], rec["rollout_time_idx"] = succ, rew, dur, g[:, 3]
             rec["episode"], rec["slot"], rec["world_idx"], rec["bad_state"] = h[:, 0], h[:, 1], h[:, 2], h[:, 3]
             self.episode_records = rec
+        metrics = getattr(self, "_metrics", None) is not None
+        if metrics:
+            self._metrics_finish(self._episode_world)
         if rank == 0:
             for e in range(len(succ)):
                 print(f"Rollout result: {'success' if succ[e] else 'failure'}", flush=True)
                 self.result["success"].append(bool(succ[e]))
                 self.result["reward"].append(float(rew[e]))
                 self.result["duration"].append(float(dur[e]))
+            if metrics:
+                self._append_metrics_result()
             if self.args.result_filename is not None:
                 print(f"[{self.__class__.__name__}] Save the rollout results: {self.args.result_filename}")
                 with open(self.args.result_filename, "w") as f:
                     yaml.dump(self.result, f)
             self.bad_state_episodes = nbad
             self.print_statistics()
+            if metrics:
+                self._print_metrics(succ)
 
     def save_rgb_images(self, v=None):
         """RolloutBase.save_rgb_image (:541-561) for every env: the last frame of all cameras side

@@ -38,3 +38,27 @@ def gather_results(local, device, group=None):
     out = [torch.empty_like(pad) for _ in range(world)]
     dist.all_gather(out, pad, group=group)
     return torch.cat([o[: int(s.item())] for o, s in zip(out, sizes)]).cpu().numpy()
+
+
+def gather_table(local, device, group=None):
+    """All-gather [n_local, C] f64 rows from every rank (variable n_local allowed, C the same on all
+    ranks): gather_results for any number of columns.  Returns the [n_total, C] array in global
+    order.  Values pass through bit for bit (no arithmetic), so integers up to 2^53 are exact."""
+    import torch.distributed as dist
+
+    world = dist.get_world_size(group)
+    local = np.ascontiguousarray(local, dtype=np.float64)
+    if local.ndim != 2:
+        raise ValueError(f"gather_table takes a [n, C] array, got shape {local.shape}")
+    t = torch.as_tensor(local, dtype=torch.float64, device=device)
+    n = torch.tensor([t.shape[0], t.shape[1]], dtype=torch.int64, device=device)
+    sizes = [torch.zeros_like(n) for _ in range(world)]
+    dist.all_gather(sizes, n, group=group)
+    if any(int(s[1].item()) != t.shape[1] for s in sizes):
+        raise ValueError(f"gather_table: the ranks disagree on the column count {[int(s[1].item()) for s in sizes]}")
+    m = int(max(int(s[0].item()) for s in sizes))
+    pad = torch.zeros((m, t.shape[1]), dtype=torch.float64, device=device)
+    pad[: t.shape[0]] = t
+    out = [torch.empty_like(pad) for _ in range(world)]
+    dist.all_gather(out, pad, group=group)
+    return torch.cat([o[: int(s[0].item())] for o, s in zip(out, sizes)]).cpu().numpy()

@@ -550,6 +550,98 @@ class EpisodeTrace:
         return {name: h.numpy() for name, h in host.items()}
 
 
+class EpisodeMetrics:
+    """The per-episode metrics table of rmbx_episode_metrics and the per-slot history it needs,
+    shape-checked once.  `engine` needs the PhysicsEngine tensors (qpos, qvel, _ctrl_store,
+    sensordata and nq / nv / nu) and, unless `ee_pos` is given, `info.site` and ws("sxpos"): the
+    end-effector point is the world position of `site`, a strided [n, 3] view of the engine's
+    workspace.  count rows, one per episode episode_base .. episode_base + count - 1;
+    slot_episode i32 [n] (None: slot e holds episode episode_base + e, a lockstep run), bad_resets
+    i32 [n] (None: no divergence guard), n_pre the phase index of RolloutPhase (sched_active's),
+    arm_qadr / arm_dof the qpos / qvel addresses of the six arm joints."""
+
+    def __init__(self, sched, engine, n_pre, count, episode_base=0, slot_episode=None, bad_resets=None, site="pinch",
+                 arm_qadr=None, arm_dof=None, ee_pos=None):
+        n, dev = sched.shape[0], sched.device
+        nq, nv, nu = int(engine.nq), int(engine.nv), int(engine.nu)
+        count = int(count)
+        if count < 0:
+            raise ValueError(f"count must not be negative, got {count}")
+        if arm_qadr is None or arm_dof is None:
+            raise ValueError("arm_qadr and arm_dof (the qpos / qvel addresses of the six arm joints) are required")
+        arm_qadr, arm_dof = [int(x) for x in arm_qadr], [int(x) for x in arm_dof]
+        if len(arm_qadr) != 6 or len(arm_dof) != 6:
+            raise ValueError("arm_qadr and arm_dof must have 6 entries each")
+        if min(arm_qadr) < 0 or max(arm_qadr) >= nq or min(arm_dof) < 0 or max(arm_dof) >= nv:
+            raise ValueError(f"arm addresses out of range: qpos {arm_qadr} of {nq}, qvel {arm_dof} of {nv}")
+        if nu < 6:
+            raise ValueError(f"the metrics read the six arm commands: nu must be at least 6, got {nu}")
+        _chk(sched, torch.uint8, (n, N.SCHED_DTYPE.itemsize), "sched")
+        _chk(engine.qpos, torch.float64, (n, nq), "qpos")
+        _chk(engine.qvel, torch.float64, (n, nv), "qvel")
+        _chk(engine._ctrl_store, torch.float64, None, "ctrl")
+        if engine._ctrl_store.dim() != 2 or engine._ctrl_store.shape[0] != n or engine._ctrl_store.shape[1] < nu:
+            raise ValueError("ctrl must be [n, >= nu]")
+        _chk(engine.sensordata, torch.float64, (n, 6), "sensordata")
+        if slot_episode is not None:
+            _chk(slot_episode, torch.int32, (n,), "slot_episode")
+        if bad_resets is not None:
+            _chk(bad_resets, torch.int32, (n,), "bad_resets")
+        if ee_pos is None:
+            if site not in engine.info.site:
+                raise ValueError(f"the scene has no site {site!r}")
+            i = int(engine.info.site[site])
+            ee_pos = engine.ws("sxpos")[:, 3 * i: 3 * i + 3]
+        # a strided view: 3 contiguous doubles per slot, rows a whole number of doubles apart
+        if not isinstance(ee_pos, torch.Tensor) or not ee_pos.is_cuda or ee_pos.dtype != torch.float64:
+            raise ValueError("ee_pos must be a float64 device tensor")
+        if tuple(ee_pos.shape) != (n, 3) or ee_pos.stride(1) != 1 or (n > 1 and ee_pos.stride(0) < 3):
+            raise ValueError(f"ee_pos must be [n, 3] with unit inner stride and a row stride of at least 3 (got shape "
+                             f"{tuple(ee_pos.shape)}, strides {ee_pos.stride()})")
+        for name, t in (("qpos", engine.qpos), ("qvel", engine.qvel), ("ctrl", engine._ctrl_store),
+                        ("sensordata", engine.sensordata), ("slot_episode", slot_episode), ("bad_resets", bad_resets),
+                        ("ee_pos", ee_pos)):
+            if t is not None and t.device != dev:
+                raise ValueError(f"{name} must be on the schedule's device {dev} (got {t.device})")
+        self.n, self.count, self.episode_base, self.n_pre = n, count, int(episode_base), int(n_pre)
+        self.sched, self.engine, self.ee_pos = sched, engine, ee_pos
+        self.slot_episode, self.bad_resets = slot_episode, bad_resets
+        self.rows = torch.zeros((count, N.METRICS_DTYPE.itemsize), dtype=torch.uint8, device=dev)  # steps 0: empty
+        self.hist = torch.zeros((n, N.METRICS_HIST), dtype=torch.float64, device=dev)
+        b = N.MetricsBuffers()
+        for name, t in (("sched", sched), ("slot_episode", slot_episode), ("bad_resets", bad_resets),
+                        ("qpos", engine.qpos), ("qvel", engine.qvel), ("ctrl", engine._ctrl_store),
+                        ("sensordata", engine.sensordata), ("ee_pos", ee_pos), ("table", self.rows),
+                        ("hist", self.hist)):
+            setattr(b, name, N.ptr(t))
+        b.n_env, b.n_episodes, b.episode_base, b.n_pre = n, count, self.episode_base, self.n_pre
+        b.nq, b.nv, b.nu, b.ctrl_stride = nq, nv, nu, engine._ctrl_store.shape[1]
+        b.ee_stride = int(ee_pos.stride(0)) if n > 1 else max(int(ee_pos.stride(0)), 3)
+        for j in range(6):
+            b.arm_qadr[j], b.arm_dof[j] = arm_qadr[j], arm_dof[j]
+        self._bufs = b
+
+    def step(self, active, reward):
+        """One env-step (rmbx_episode_metrics), between the physics step and sched_update: active u8
+        [n] is the mask the step ran under (None: all), reward f64 [n] the step's reward.  No host
+        synchronisation."""
+        import ctypes
+
+        if active is not None:
+            _chk(active, torch.uint8, (self.n,), "active")
+        _chk(reward, torch.float64, (self.n,), "reward")
+        for name, t in (("active", active), ("reward", reward)):
+            if t is not None and t.device != self.sched.device:
+                raise ValueError(f"{name} must be on the schedule's device {self.sched.device} (got {t.device})")
+        self._bufs.active, self._bufs.reward = N.ptr(active), N.ptr(reward)
+        N.call("rmbx_episode_metrics", ctypes.byref(self._bufs), N.stream_ptr())
+
+    def table(self):
+        """Host structured array (N.METRICS_DTYPE) of the `count` rows, in episode order: the one
+        device read, at the end of the run."""
+        return self.rows.cpu().numpy().view(N.METRICS_DTYPE).reshape(-1).copy()
+
+
 # ------------------------------------------------------------------------------------------
 # Vision-trunk epilogues (NHWC = torch channels_last)
 # ------------------------------------------------------------------------------------------

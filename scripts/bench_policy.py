@@ -62,6 +62,8 @@ def parse_args(argv=None):
                    help="samples per pixel of the camera images (Rollout.py --offsamples)")
     p.add_argument("--sampler_noise", choices=["batch", "episode"], default=None,
                    help="the diffusion policies' noise source (Rollout.py --sampler_noise; default: batch)")
+    p.add_argument("--episode_metrics", action="store_true",
+                   help="accumulate the per-episode metrics every env-step (Rollout.py --episode_metrics): its cost")
     a = p.parse_args(argv)
     if a.sampler_noise is not None and not a.policy.startswith("DiffusionPolicy"):
         p.error("--sampler_noise is a flag of the diffusion policies")
@@ -75,7 +77,8 @@ def rollout_argv(a):
     return (["--num_envs", str(a.num_envs), "--device", "cuda:0", "--world_idx_list", *[str(i) for i in range(6)],
              "--world_random_scale", "0.01", "0.01", "0.0", "--seed", "0", "--precision", a.precision,
              "--shadows", a.shadows, "--offsamples", a.offsamples] + (["--tactile"] if a.tactile else [])
-            + (["--sampler_noise", a.sampler_noise] if a.sampler_noise else []))
+            + (["--sampler_noise", a.sampler_noise] if a.sampler_noise else [])
+            + (["--episode_metrics"] if a.episode_metrics else []))
 
 
 def main():
@@ -137,6 +140,7 @@ def main():
                       "scene": a.env + (" minus YCB_sim" if a.env == "MujocoUR5ePick" else ""),
                       "tactile": "synthetic, every env-step" if a.tactile else None, "shadows": a.shadows,
                       "offsamples": a.offsamples, "sampler_noise": a.sampler_noise,
+                      "episode_metrics": bool(a.episode_metrics),
                       "data": "synthetic (random-init weights)"}), flush=True)
 
 
