@@ -1027,6 +1027,69 @@ int rmbx_philox_normal(uint64_t seed, const int32_t* episode, const int32_t* dra
                        void* out, int n, int L, int kind, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Per-episode observation perturbation (opt-in, --perturb): what the policy reads -- the RGB frame
+ * of a camera and the normalised state -- perturbed on the device by a rule keyed like the sampler
+ * noise above, so that an episode sees the same perturbation in any slot, slot count, shard or
+ * re-run.  info["rgb_images"], the trace and the saved images stay clean; depth, point-cloud
+ * geometry, physics and commands are not touched.
+ *
+ * The rule, for one camera frame rgb u8 [n][H][W][3], episode i32 [n], draw i32 [n] (the episode's
+ * own rollout_time_idx at the observation) and camera = the camera's index in the scene's camera
+ * list, in [0, 255].  All randomness is the Philox4x32-10 rule of rmbx_philox_normal: key = seed,
+ * counter (block j, plane, draw, episode).  The planes lie above the sampler's:
+ *   RMBX_PERTURB_PLANE_PHOTO  0x40000000            draw 0     episode-constant lighting, all cameras
+ *   RMBX_PERTURB_PLANE_OCC    0x40000100 + camera   draw 0     episode-constant occluder of the camera
+ *   RMBX_PERTURB_PLANE_NOISE  0x40000200 + camera   draw       per-frame sensor noise
+ *   RMBX_PERTURB_PLANE_STATE  0x40000300            draw       per-observation state noise
+ * Uniforms: u(w) = ((w >> 9) + 0.5) * 2^-23, exact in f32, inside (0, 1).  Arithmetic: f32, no
+ * contraction, each operation rounded once, in the order written (numpy f32 reproduces the bits).
+ * Episode constants, from the words w0..w7 of blocks 0 and 1 of the PHOTO and of the OCC plane:
+ *   PHOTO  b = B * (2 * u(w0) - 1);  c = 1 + C * (2 * u(w1) - 1);
+ *          g_k = 1 + G * (2 * u(w_{2+k}) - 1), channel k = 0, 1, 2
+ *   OCC    (only when occ_h > 0)  y0 = (int)(u(w0) * (float)(H - occ_h + 1)),
+ *          x0 = (int)(u(w1) * (float)(W - occ_w + 1)), truncating; colour o_k = (float)(w_{2+k} >> 24)
+ * Element i = (y * W + x) * 3 + k of a row:
+ *   1. v = (float)rgb[i]
+ *   2. v = (v - 127.5f) * c          3. v = v + 127.5f         (2, 3: only when C != 0)
+ *   4. v = v * g_k                   (only when G != 0)
+ *   5. v = v + b                     (only when B != 0)
+ *   6. v = o_k where (y, x) lies in [y0, y0 + occ_h) x [x0, x0 + occ_w)
+ *   7. v = v + sigma * z_i           (only when sigma > 0): z_i is, bit for bit, the normal that
+ *      rmbx_philox_normal gives element i of a row of length L = H * W * 3 at (seed, episode, draw,
+ *      NOISE plane + camera) -- the same device functions (csrc/rmbx_philox.h)
+ *   8. out[i] = (uint8_t)min(max(rintf(v), 0.f), 255.f)
+ * A component of strength zero is skipped, so the all-zero parameters return the input bytes.
+ * The policy forms derive from the perturbed 8-bit pixel u exactly as the renderer derives them from
+ * the rendered one: ((float)u / 255.0f - mean) / std, policy_dtype 0 = f32 [n][3][H][W], 1 = bf16
+ * [n][3][H][W], 2 / 3 / 4 = the 2x2 space-to-depth [n][H/2][W/2][16] in bf16 / f32 / u8 (the 8-bit
+ * value itself), channel (dy * 2 + dx) * 3 + k, channels 12..15 zero.
+ * State noise (done by the caller with rmbx_philox_normal): the normalised f32 state [n][state_dim]
+ * becomes s + (z * s_sigma), z the normals of the STATE plane with L = state_dim and the same draw.
+ *
+ * rmbx_image_perturb: rgb_out and policy are optional, at least one is given; rgb_out == rgb is
+ * allowed (the operation is elementwise), any other overlap of the three buffers is refused.
+ * active u8 [n] optional: nothing is written to any output of a row with active == 0.
+ * brightness in [0, 255], contrast and gain in [0, 1), noise_sigma >= 0, 0 <= occ_h <= H,
+ * 0 <= occ_w <= W, std != 0 with a policy output, H and W even for the space-to-depth forms,
+ * H, W <= 8192, n * H * W * 3 < 2^31 (RMBX_ERR_ARG otherwise, before the one launch).
+ * ------------------------------------------------------------------------------------------- */
+#define RMBX_PERTURB_PLANE_PHOTO 0x40000000
+#define RMBX_PERTURB_PLANE_OCC 0x40000100
+#define RMBX_PERTURB_PLANE_NOISE 0x40000200
+#define RMBX_PERTURB_PLANE_STATE 0x40000300
+
+typedef struct rmbx_perturb_params {
+  float brightness, contrast, gain, noise_sigma; /* B (levels), C, G in [0, 1), sigma (levels) */
+  int32_t occ_h, occ_w;                          /* occluder size in pixels; 0, 0 = none */
+  float mean[3], std[3];                         /* for the policy forms */
+} rmbx_perturb_params;
+
+int rmbx_image_perturb(const uint8_t* rgb, uint8_t* rgb_out, void* policy, int policy_dtype,
+                       const rmbx_perturb_params* p, uint64_t seed, const int32_t* episode,
+                       const int32_t* draw, int camera, const uint8_t* active, int n, int H, int W,
+                       void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Policy-input image preprocessing, batched over envs.
  * rmbx_resize_crop_u8: src u8 [n][H][W][C] (renderer frames) -> dst [n][C][ch][cw] (f32 dtype 0 /
  * bf16 dtype 1) = (v * (1/255)) * a + b, v = cv2.resize(src, (rw, rh), INTER_LINEAR)[y0+y, x0+x];

@@ -119,6 +119,8 @@ SIGNATURES = {
     "rmbx_ddpm_step": (_c_int, [_c_p] * 4 + [_c_sz, _c_p, _c_p]),
     "rmbx_ddim_step": (_c_int, [_c_p] * 3 + [_c_sz, _c_p, _c_int, _c_p]),
     "rmbx_philox_normal": (_c_int, [ctypes.c_uint64, _c_p, _c_p, _c_int, _c_int, _c_p, _c_int, _c_int, _c_int, _c_p]),
+    "rmbx_image_perturb": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_p, ctypes.c_uint64, _c_p, _c_p, _c_int, _c_p, _c_int,
+                                    _c_int, _c_int, _c_p]),
     "rmbx_resize_crop_u8": (_c_int, [_c_p] + [_c_int] * 10 + [ctypes.c_float, ctypes.c_float, _c_p, _c_int, _c_p]),
     "rmbx_resize_f32": (_c_int, [_c_p, _c_p] + [_c_int] * 5 + [_c_p]),
     "rmbx_pointcloud_fps": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_int, _c_d, _c_p, _c_p, _c_int, _c_int,
@@ -253,6 +255,20 @@ METRICS_DTYPE = np.dtype(
 assert METRICS_DTYPE.itemsize == 72
 METRICS_BAD_STATE = 1  # include/rmbx.h RMBX_METRICS_BAD_STATE
 METRICS_HIST = 21  # include/rmbx.h RMBX_METRICS_HIST
+
+
+class PerturbParams(ctypes.Structure):
+    """rmbx_perturb_params (include/rmbx.h)."""
+
+    _fields_ = [("brightness", ctypes.c_float), ("contrast", ctypes.c_float), ("gain", ctypes.c_float),
+                ("noise_sigma", ctypes.c_float), ("occ_h", ctypes.c_int32), ("occ_w", ctypes.c_int32),
+                ("mean", ctypes.c_float * 3), ("std", ctypes.c_float * 3)]
+
+
+assert ctypes.sizeof(PerturbParams) == 48
+# include/rmbx.h RMBX_PERTURB_PLANE_*
+PERTURB_PLANE_PHOTO, PERTURB_PLANE_OCC, PERTURB_PLANE_NOISE, PERTURB_PLANE_STATE = (
+    0x40000000, 0x40000100, 0x40000200, 0x40000300)
 
 _lib = None
 

@@ -2,12 +2,17 @@
 
   python -m robomanipbaselines_amd.bin.Replay TRACE_DIR --episode 4117 [--steps last | all | k1 k2 ...]
       [--cameras front side ...] [--shadows off|scene] [--offsamples 1|4|scene] [--output_image_dir D]
+      [--as_seen]
 
 A trace row (--trace_dir of bin/Rollout.py, common/episode_trace.py) holds the four per-env arrays
 the renderer reads.  The renderer's output does not depend on the batch, so the chosen rows are
 drawn in one call per camera with the steps as the batch dimension, and every image is bit for bit
 the frame of the live step.  The cameras go side by side, as --save_last_image writes them, to
 Rollout<Policy>_<Env>_world<idx>_<success|failure>_ep<episode>_step<k>.png.
+
+--as_seen (a run recorded with --perturb): the header's perturbation is applied to the re-rendered
+frame with the row's episode and rollout_time_idx, the keys the live run used, so the image of a step
+the policy read is the frame it read (the trace itself holds the clean scene).
 """
 
 import argparse
@@ -71,10 +76,24 @@ def make_renderer(header, device, shadows=None, offsamples=None):
                     samples=samples)
 
 
-def render_rows(renderer, rows, idx, cameras, device, batch_bytes=BATCH_BYTES):
+def as_seen_of(header):
+    """The (spec, seed, camera list) --as_seen applies: the recording run's --perturb.  ValueError for
+    a trace recorded without it."""
+    from ..common.perturb import spec_from_dict
+
+    if header.get("perturb") is None:
+        raise ValueError("--as_seen needs a trace recorded with --perturb: this trace's header has no `perturb` key "
+                         "(the policy read the clean frames, which Replay draws without --as_seen)")
+    return spec_from_dict(header["perturb"]), int(header["seed"]) & (2**64 - 1), list(header["camera_names"])
+
+
+def render_rows(renderer, rows, idx, cameras, device, batch_bytes=BATCH_BYTES, as_seen=None):
     """u8 [len(idx), H, W * len(cameras), 3] host array: the rows `idx` of the episode drawn by every
-    camera, the cameras side by side.  The steps are the renderer's batch, in batches that fit."""
+    camera, the cameras side by side.  The steps are the renderer's batch, in batches that fit.
+    as_seen: as_seen_of(header), to perturb every frame as the policy of the recording run saw it."""
     import torch
+
+    from .. import kernels as K
 
     H, W = renderer.height, renderer.width
     ngeom, nbody = rows["gxpos"].shape[1], rows["xpos"].shape[1]
@@ -91,6 +110,14 @@ def render_rows(renderer, rows, idx, cameras, device, batch_bytes=BATCH_BYTES):
         rgb = torch.empty((t, H, W, 3), dtype=torch.uint8, device=device)
         for c, cam in enumerate(cameras):
             renderer.render(eng, cam, rgb=rgb)
+            if as_seen is not None and as_seen[0].touches_images:
+                spec, seed, scene_cameras = as_seen
+                episode = torch.from_numpy(np.ascontiguousarray(rows["episode"][sel], dtype=np.int32)).to(device)
+                draw = torch.from_numpy(np.ascontiguousarray(rows["rollout_time_idx"][sel], dtype=np.int32)).to(device)
+                occ_h, occ_w = spec.occ_size(H, W)
+                K.image_perturb(rgb, seed, episode, draw, scene_cameras.index(cam), brightness=spec.brightness,
+                                contrast=spec.contrast, gain=spec.gain, noise=spec.noise, occ_h=occ_h, occ_w=occ_w,
+                                rgb_out=rgb)
             out[b0:b0 + t, :, c * W:(c + 1) * W] = rgb.cpu().numpy()
     return out
 
@@ -113,6 +140,8 @@ def main(argv=None):
     parser.add_argument("--offsamples", choices=["1", "4", "scene"], default=None, help="default: the recording run's")
     parser.add_argument("--output_image_dir", type=str, default=".")
     parser.add_argument("--device", type=str, default="cuda:0")
+    parser.add_argument("--as_seen", action="store_true",
+                        help="apply the recording run's --perturb to the frames: what the policy read")
     args = parser.parse_args(argv)
     # everything that can be wrong with the request is found before the device is touched
     reader = TraceReader(args.trace_dir)
@@ -124,6 +153,7 @@ def main(argv=None):
     unknown = [c for c in cameras if c not in header["camera_names"]]
     if unknown:
         raise ValueError(f"unknown camera(s) {unknown}; the scene has {header['camera_names']}")
+    as_seen = as_seen_of(header) if args.as_seen else None
     from ..common.image_io import write_png
 
     renderer = make_renderer(header, args.device, args.shadows, args.offsamples)
@@ -135,7 +165,7 @@ def main(argv=None):
     group = int(max(1, BATCH_BYTES // per_image))
     for g0 in range(0, len(idx), group):
         part = idx[g0:g0 + group]
-        images = render_rows(renderer, rows, part, cameras, args.device)
+        images = render_rows(renderer, rows, part, cameras, args.device, as_seen=as_seen)
         for i, image in zip(part, images):
             path = os.path.abspath(os.path.join(args.output_image_dir, image_name(header, record, rows["step"][i])))
             write_png(path, image)

@@ -37,6 +37,7 @@ from ..common import episode_metrics as EM
 from ..common.data_key import DataKey, action_key_codes, state_key_codes
 from ..common.data_utils import make_meta_info
 from ..common.episode_trace import TraceWriter, parse_episodes, row_bytes, select_mask
+from ..common.perturb import Perturber, parse_spec
 
 
 class PhaseSpec:
@@ -59,6 +60,8 @@ class BatchedRolloutBase:
         self.setup_args(argv=argv)
         for k, v in overrides.items():
             setattr(self.args, k, v)
+        # the parsed --perturb spec (None: off); ValueError for a bad key or value
+        self.perturb_spec = None if getattr(self.args, "perturb", None) is None else parse_spec(self.args.perturb)
         torch.manual_seed(self.args.seed)
         np.random.seed(self.args.seed)
         self.device = torch.device(self.args.device)
@@ -76,6 +79,7 @@ class BatchedRolloutBase:
         self.phase_timer = None  # optional PhaseTimer (common/phase_timer.py): bench.py's per-phase split
         self._trace = None  # the TraceWriter of a run with --trace_dir
         self._metrics = None  # the kernels.EpisodeMetrics accumulator of a run with --episode_metrics
+        self._perturb = None  # the common.perturb.Perturber of a run with --perturb
 
     def attach_phase_timer(self, timer):
         """Record HIP events at the policy / render / physics / glue boundaries of every env-step
@@ -163,6 +167,12 @@ class BatchedRolloutBase:
                                  "success, peak wrist force / torque, peak joint speed and tracking error, gripper and "
                                  "joint path lengths, command roughness): a `metrics` key in the result file and a "
                                  "summary with the success rate's Wilson interval after the statistics")
+        parser.add_argument("--perturb", type=str, nargs="+", default=None, metavar="KEY=VALUE",
+                            help="perturb what the policy observes, per episode and on the device (the rule: "
+                                 "include/rmbx.h, rmbx_image_perturb): brightness=LEVELS contrast=C gain=G (C, G in "
+                                 "[0, 1)), noise=LEVELS (sensor noise), occluder=F (a rectangle of F x each image "
+                                 "side), state_noise=S (normalised units). An episode sees the same perturbation in "
+                                 "any slot, shard or re-run; info['rgb_images'], saved images and the trace stay clean")
         if self.require_task_desc:
             parser.add_argument("--task_desc", type=str, required=True)
         self.set_additional_args(parser)
@@ -179,6 +189,8 @@ class BatchedRolloutBase:
         if self.args.trace_stride < 1:
             raise ValueError("--trace_stride must be at least 1")
         parse_episodes(self.args.trace_episodes)  # ValueError for anything but `all` or indices
+        if self.args.perturb is not None:
+            parse_spec(self.args.perturb)  # ValueError for a bad key or value
         if self.args.num_episodes is not None:
             if self.args.num_episodes < 1:
                 raise ValueError("--num_episodes must be at least 1")
@@ -250,8 +262,12 @@ class BatchedRolloutBase:
                               self._state_codes, self.state_dim)
 
     def get_state(self):
-        """RolloutBase.get_state (:463-477): the routed state, normalised, as f32 [n, state_dim]."""
-        return self.normalize_state(self.get_raw_state())
+        """RolloutBase.get_state (:463-477): the routed state, normalised, as f32 [n, state_dim]
+        (--perturb state_noise: plus the episode's state noise of this observation)."""
+        s = self.normalize_state(self.get_raw_state())
+        if getattr(self, "_perturb", None) is not None:
+            s = self._perturb_rows().state(s)
+        return s
 
     def normalize_state(self, x):
         """normalize_data (DataUtils.py:9-24) in f64 (same operations and order as numpy), then the
@@ -292,7 +308,17 @@ class BatchedRolloutBase:
             self._img = torch.empty((self.n, len(self.camera_names)) + shape, dtype=dtype, device=self.device)
             self._img_cam = [torch.empty((self.n,) + shape, dtype=dtype, device=self.device) for _ in self.camera_names]
         self._mark("render")
-        if len(self.camera_names) == 1:
+        if getattr(self, "_perturb", None) is not None and self.perturb_spec.touches_images:
+            # the clean u8 frame is rendered, and the kernel writes the policy form of the perturbed one
+            pt = self._perturb_rows()
+            for i, cam in enumerate(self.camera_names):
+                rgb = self.info["rgb_images"][cam]
+                if len(self.camera_names) == 1:
+                    pt.policy(cam, rgb, self._img.view((self.n,) + shape), mean, std)
+                else:
+                    pt.policy(cam, rgb, self._img_cam[i], mean, std)
+                    self._img[:, i].copy_(self._img_cam[i])
+        elif len(self.camera_names) == 1:
             self.env.render_images(self.camera_names[0], policy=self._img.view((self.n,) + shape), mean=mean, std=std)
         else:
             for i, cam in enumerate(self.camera_names):
@@ -300,6 +326,36 @@ class BatchedRolloutBase:
                 self._img[:, i].copy_(self._img_cam[i])
         self._mark("policy")
         return self._img
+
+    # -- observation perturbation (--perturb) ------------------------------------------------------
+    def _perturb_begin(self):
+        """The Perturber of this run, and its one printed line."""
+        r = self.env.renderer
+        self._perturb = Perturber(self.perturb_spec, self.args.seed, self.n, r.height, r.width, self.env.camera_names,
+                                  self.device)
+        self._lockstep_rows = torch.arange(self.args.env_offset, self.args.env_offset + self.n, dtype=torch.int32,
+                                           device=self.device)
+        print(f"[{self.__class__.__name__}] Perturb: {self.perturb_spec}", flush=True)
+
+    def _perturb_rows(self):
+        """The Perturber with the rows' (episode, draw) of the observation being made.  Lockstep: env e
+        is episode env_offset + e and every row's draw is the host's rollout_time_idx; streaming: the
+        stream's slot -> episode map and each slot's own rollout_time_idx, read from the schedule on
+        the device."""
+        pt = self._perturb
+        if self.args.num_episodes is not None and getattr(self, "stream", None) is not None:
+            pt.set_rows(self.stream.slot_episode, self.sched.view(torch.int32)[:, 1])
+        else:
+            pt.set_rows(self._lockstep_rows, int(self.rollout_time_idx))
+        return pt
+
+    def policy_rgb(self, cam):
+        """The 8-bit frame of camera `cam` the policy reads: info["rgb_images"][cam], or with --perturb
+        the perturbed scratch frame (info["rgb_images"] itself stays clean)."""
+        rgb = self.info["rgb_images"][cam]
+        if getattr(self, "_perturb", None) is None or not self.perturb_spec.touches_images:
+            return rgb
+        return self._perturb_rows().frame(cam, rgb)
 
     # -- command routing (MotionManager / ArmManager) ------------------------------------------
     def _reset_motion(self):
@@ -364,6 +420,9 @@ class BatchedRolloutBase:
         self.rollout_time_idx = 0
         self.policy_action = torch.zeros((self.n, self.action_dim), dtype=torch.float64, device=dev)
         self.reset_variables()
+        self._perturb = None
+        if getattr(self, "perturb_spec", None) is not None:
+            self._perturb_begin()
         if getattr(self.args, "trace_dir", None) and self.args.num_episodes is None:
             self._trace_begin()
         if getattr(self.args, "episode_metrics", False) and self.args.num_episodes is None:
@@ -446,6 +505,8 @@ class BatchedRolloutBase:
         }
         if hasattr(a, "sampler_noise"):  # the diffusion policies: which noise a re-run must ask for
             header["sampler_noise"] = str(a.sampler_noise)
+        if getattr(self, "perturb_spec", None) is not None:  # what Replay --as_seen applies
+            header["perturb"] = self.perturb_spec.as_dict()
         self._trace = TraceWriter(directory, header, trace)
         # the size the run can reach: an episode ends by max_duration + the post-success second
         dt = env.frame_skip * env.sim_timestep
@@ -767,6 +828,8 @@ class BatchedRolloutBase:
                 self.result["duration"].append(float(dur[e]))
             if metrics:
                 self._append_metrics_result()
+            if getattr(self, "perturb_spec", None) is not None:
+                self.result["perturb"] = self.perturb_spec.as_dict()
         if self.args.save_last_image:
             self.save_rgb_images(v)
         if rank == 0 and self.args.result_filename is not None:
@@ -819,6 +882,8 @@ class BatchedRolloutBase:
                 self.result["duration"].append(float(dur[e]))
             if metrics:
                 self._append_metrics_result()
+            if getattr(self, "perturb_spec", None) is not None:
+                self.result["perturb"] = self.perturb_spec.as_dict()
             if self.args.result_filename is not None:
                 print(f"[{self.__class__.__name__}] Save the rollout results: {self.args.result_filename}")
                 with open(self.args.result_filename, "w") as f:

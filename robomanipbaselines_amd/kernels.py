@@ -5,6 +5,7 @@ enqueued on the current torch stream.  Shape errors raise ValueError, as the ref
 MotionManager/DataKey do for bad keys (common/manager/MotionManager.py:36-39).
 """
 
+import ctypes
 import os
 import numpy as np
 import torch
@@ -788,6 +789,56 @@ def philox_normal(seed, episode, draw, out, plane0=0, L=None, words=False):
     N.call("rmbx_philox_normal", seed, N.ptr(episode), N.ptr(draw), plane0, nplane, N.ptr(out), n, L,
            1 if words else 0, N.stream_ptr())
     return out
+
+
+# ------------------------------------------------------------------------------------------
+# Per-episode observation perturbation (--perturb)
+# ------------------------------------------------------------------------------------------
+def image_perturb(rgb, seed, episode, draw, camera, brightness=0.0, contrast=0.0, gain=0.0, noise=0.0, occ_h=0,
+                  occ_w=0, rgb_out=None, policy=None, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0), active=None):
+    """The perturbation rule of include/rmbx.h (rmbx_image_perturb) on one camera's frames.
+
+    rgb u8 [n, H, W, 3]; episode, draw i32 [n]; camera: the camera's index in the scene's camera list.
+    rgb_out u8 [n, H, W, 3] (rgb itself: in place) and / or policy, one of the renderer's policy
+    forms ([n, 3, H, W] f32 / bf16 or the space-to-depth [n, H/2, W/2, 16] bf16 / f32 / u8) with its
+    mean / std; at least one of the two.  active u8 [n]: rows with 0 are not written.  Shapes and
+    dtypes are checked before the device.  Returns (rgb_out, policy)."""
+    seed = int(seed)
+    if not 0 <= seed < 2**64:
+        raise ValueError(f"seed must be an unsigned 64-bit value (got {seed})")
+    _chk(rgb, torch.uint8, name="rgb")
+    if rgb.dim() != 4 or rgb.shape[3] != 3 or rgb.shape[0] < 1:
+        raise ValueError(f"rgb must have shape [n, H, W, 3], n >= 1 (got {tuple(rgb.shape)})")
+    n, H, W, _ = (int(v) for v in rgb.shape)
+    _chk(episode, torch.int32, (n,), "episode")
+    _chk(draw, torch.int32, (n,), "draw")
+    if rgb_out is None and policy is None:
+        raise ValueError("one of rgb_out and policy must be given")
+    pdt = 0
+    if rgb_out is not None:
+        _chk(rgb_out, torch.uint8, (n, H, W, 3), "rgb_out")
+    if policy is not None:
+        if not isinstance(policy, torch.Tensor) or policy.dtype not in (torch.float32, torch.bfloat16, torch.uint8):
+            raise ValueError("policy must be an f32, bf16 or u8 tensor")
+        if H % 2 == 0 and W % 2 == 0 and tuple(policy.shape) == (n, H // 2, W // 2, 16):
+            pdt = {torch.bfloat16: 2, torch.float32: 3, torch.uint8: 4}[policy.dtype]
+        elif policy.dtype == torch.uint8:
+            raise ValueError("a uint8 policy tensor must be the space-to-depth form [n, H/2, W/2, 16]")
+        else:
+            pdt = 1 if policy.dtype == torch.bfloat16 else 0
+        _chk(policy, policy.dtype, (n, H // 2, W // 2, 16) if pdt >= 2 else (n, 3, H, W), "policy")
+    if active is not None:
+        _chk(active, torch.uint8, (n,), "active")
+    for t, name in ((episode, "episode"), (draw, "draw"), (rgb_out, "rgb_out"), (policy, "policy"), (active, "active")):
+        if t is not None and t.device != rgb.device:
+            raise ValueError(f"{name} is on {t.device}, rgb on {rgb.device}")
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("mean and std must have three entries")
+    p = N.PerturbParams(float(brightness), float(contrast), float(gain), float(noise), int(occ_h), int(occ_w),
+                        (ctypes.c_float * 3)(*[float(v) for v in mean]), (ctypes.c_float * 3)(*[float(v) for v in std]))
+    N.call("rmbx_image_perturb", N.ptr(rgb), N.ptr(rgb_out), N.ptr(policy), pdt, ctypes.byref(p), seed, N.ptr(episode),
+           N.ptr(draw), int(camera), N.ptr(active), n, H, W, N.stream_ptr())
+    return rgb_out, policy
 
 
 # ------------------------------------------------------------------------------------------

@@ -140,7 +140,7 @@ class RolloutDiffusionPolicy(BatchedRolloutBase):
         crop = ((rh - ch) // 2, (rw - cw) // 2, ch, cw)
         imgs = []
         for cam in self.camera_names:
-            rgb = self.info["rgb_images"][cam]
+            rgb = self.policy_rgb(cam)
             imgs.append(K.resize_crop_u8(rgb, (rw, rh), crop, a=2.0, b=-1.0, dtype=dtype))
         img = torch.stack(imgs, dim=1)  # [n, ncam, 3, ch, cw]
         if self.images_buf is None:

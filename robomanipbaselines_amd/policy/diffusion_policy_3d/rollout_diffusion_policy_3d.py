@@ -66,7 +66,7 @@ class RolloutDiffusionPolicy3d(RolloutDiffusionPolicy):
         """RolloutDiffusionPolicy3d.get_pointcloud (:127-171): info["rgb_images"] and
         info["depth_images"] of the first camera from the last env-step."""
         cam = self.camera_names[0]
-        rgb, depth = self.info["rgb_images"][cam], self.info["depth_images"][cam]
+        rgb, depth = self.policy_rgb(cam), self.info["depth_images"][cam]  # --perturb: the colours only
         rw, rh = self.image_size
         rgb_s = K.resize_crop_u8(rgb, (rw, rh), None, dtype=torch.uint8)
         depth_s = K.resize_f32(depth, (rw, rh))

@@ -123,7 +123,7 @@ class RolloutSarnn(BatchedRolloutBase):
             self._img_cam = [torch.empty((self.n, 3, S, S), dtype=torch.float32, device=self.device)
                              for _ in self.camera_names]
         self._mark("render")  # the u8 frames are rendered on first access
-        frames = [self.info["rgb_images"][cam] for cam in self.camera_names]
+        frames = [self.policy_rgb(cam) for cam in self.camera_names]
         self._mark("policy")
         for i, (rgb, crop_size) in enumerate(zip(frames, self.crop_size_list)):
             y0, x0, ch, cw = crop_window(rgb.shape[1], rgb.shape[2], crop_size)

@@ -64,6 +64,8 @@ def parse_args(argv=None):
                    help="the diffusion policies' noise source (Rollout.py --sampler_noise; default: batch)")
     p.add_argument("--episode_metrics", action="store_true",
                    help="accumulate the per-episode metrics every env-step (Rollout.py --episode_metrics): its cost")
+    p.add_argument("--perturb", type=str, nargs="+", default=None, metavar="KEY=VALUE",
+                   help="perturb the policy's observation per episode (Rollout.py --perturb): its cost")
     a = p.parse_args(argv)
     if a.sampler_noise is not None and not a.policy.startswith("DiffusionPolicy"):
         p.error("--sampler_noise is a flag of the diffusion policies")
@@ -78,7 +80,8 @@ def rollout_argv(a):
              "--world_random_scale", "0.01", "0.01", "0.0", "--seed", "0", "--precision", a.precision,
              "--shadows", a.shadows, "--offsamples", a.offsamples] + (["--tactile"] if a.tactile else [])
             + (["--sampler_noise", a.sampler_noise] if a.sampler_noise else [])
-            + (["--episode_metrics"] if a.episode_metrics else []))
+            + (["--episode_metrics"] if a.episode_metrics else [])
+            + (["--perturb", *a.perturb] if a.perturb else []))
 
 
 def main():
@@ -140,7 +143,7 @@ def main():
                       "scene": a.env + (" minus YCB_sim" if a.env == "MujocoUR5ePick" else ""),
                       "tactile": "synthetic, every env-step" if a.tactile else None, "shadows": a.shadows,
                       "offsamples": a.offsamples, "sampler_noise": a.sampler_noise,
-                      "episode_metrics": bool(a.episode_metrics),
+                      "episode_metrics": bool(a.episode_metrics), "perturb": a.perturb,
                       "data": "synthetic (random-init weights)"}), flush=True)
 
 
