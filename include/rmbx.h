@@ -1090,6 +1090,83 @@ int rmbx_image_perturb(const uint8_t* rgb, uint8_t* rgb_out, void* policy, int p
                        void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Per-episode perturbation of the executed command (opt-in, --actuation): what the robot does with
+ * the policy's output -- noise and a calibration bias on the commanded action, a control delay and
+ * a lossy command link -- applied on the device between the policy's denormalised action and
+ * rmbx_motion_command, by a rule keyed like the observation perturbation above, so that an episode
+ * is actuated the same way in any slot, slot count, shard or re-run.  What the policy reads is not
+ * touched (that is --perturb); the pre-rollout reach and grasp phases and the physics are not
+ * touched either.  The command state, ctrl, the trace and the metrics show the executed command.
+ *
+ * The rule, for one env-step of the rows: action a f64 [n][A] (the policy's denormalised action
+ * of this step; held over the skip steps of an inference), episode i32 [n], r i32 [n] (the row's
+ * own rollout_time_idx at this step, r >= 0), mask_in u8 [n] (NULL = all rows active).  All
+ * randomness is the Philox4x32-10 rule of rmbx_philox_normal: key = seed, counter (block j, plane,
+ * draw, episode); u(w) = ((w >> 9) + 0.5) * 2^-23, exact in f32, inside (0, 1).  The planes lie
+ * above those of rmbx_image_perturb:
+ *   RMBX_ACTUATION_PLANE_BIAS   0x40000400   draw 0              episode constant
+ *   RMBX_ACTUATION_PLANE_NOISE  0x40000500   draw r - r % skip   the step whose inference set the action
+ *   RMBX_ACTUATION_PLANE_HOLD   0x40000600   draw r              per env-step
+ * Strengths S (noise), B (bias) in normalised action units and P (hold) are f32; D (delay) and skip
+ * are integers.  scale_k is the factor by which denormalize_data multiplies normalised action
+ * dimension k: std_k for a gaussian norm_config, range_k / (out_max - out_min) for a limits one
+ * (kernels.denorm_coeffs, the scale rmbx_act_ensemble applies).  The host computes, in f64,
+ * bs_k = (double)B * scale_k and ns_k = (double)S * scale_k and hands them over as device f64 [A].
+ * Arithmetic: f64, no contraction, each operation rounded once, in the order written (numpy
+ * reproduces the bits).  For an active row and k in [0, A):
+ *   1. v_k = a_k
+ *   2. (only when B != 0)  v_k = v_k + bs_k * (double)(2 * u(w_k) - 1); the bracket is f32, as the
+ *      symmetric uniforms of rmbx_image_perturb are; w_k is word k % 4 of block k / 4 of the BIAS
+ *      plane at draw 0
+ *   3. (only when S != 0)  v_k = v_k + ns_k * (double)z_k; z_k is, bit for bit, the normal that
+ *      rmbx_philox_normal gives element k of a row of length L = A at (seed, episode,
+ *      r - r % skip, NOISE plane) -- the same device functions (csrc/rmbx_philox.h).  The draw is
+ *      the step of the inference, so the noise is held while the action is held
+ *   4. ring[row][r % (D + 1)][k] = v_k.  The value that arrives is ring[row][(r + 1) % (D + 1)][k],
+ *      the entry written at step r - D; it is valid only when r >= D.  With D = 0 the ring has one
+ *      entry and v_k passes straight through
+ *   5. the packet is lost when P != 0 and u(w0) < P (f32 compare), w0 word 0 of block 0 of the HOLD
+ *      plane at draw r
+ *   6. mask_out[row] = 1 iff the row was active on entry, r >= D and the packet was not lost;
+ *      out[row][k] = the arrived value then.  The out of a row with mask_out = 0 is not written
+ *   7. a row with mask_in = 0 (or r < 0, which no rollout produces) writes nothing but
+ *      mask_out[row] = 0: no out, no ring entry
+ * A component of strength zero is skipped, so the all-zero parameters return the input bytes in
+ * out, and mask_out == mask_in.  The ring never needs a reset when a slot is recycled: r restarts
+ * at 0 and an entry is not read before r >= D, by when the episode itself has written it.
+ *
+ * The caller hands out and mask_out to rmbx_motion_command as its action and mask, so on a step
+ * without an arriving command the command state keeps its value (for r < D: what the pre-rollout
+ * phases left).  Its is_skip becomes that of the step the arriving command was made for,
+ * (r - D) % skip != 0 (non-negative modulo), a host scalar: lockstep rows share r, and streaming
+ * slots start their episodes on multiples of skip * infer_period_calls, so (r - D) % skip is the
+ * same for every slot in its rollout phase; rows with r < D are masked off.
+ * Bias and noise apply to every action dimension alike, the quaternion of command_eef_pose
+ * included: rmbx_motion_command builds its rotation from the unnormalised quaternion, as the
+ * reference does, and a network's own output is never a unit quaternion either.
+ *
+ * rmbx_action_perturb: one launch, no host synchronisation.  ring is caller-owned, f64
+ * [n][D + 1][A], zero or anything at first use.  out overlaps neither action nor ring.  n, A >= 1,
+ * 0 <= delay <= RMBX_ACTUATION_MAX_DELAY, skip >= 1, noise and bias finite and >= 0, hold in
+ * [0, 1), n * A * (delay + 1) < 2^31, no NULL pointer but mask_in (RMBX_ERR_ARG otherwise, before
+ * the launch).
+ * ------------------------------------------------------------------------------------------- */
+#define RMBX_ACTUATION_PLANE_BIAS 0x40000400
+#define RMBX_ACTUATION_PLANE_NOISE 0x40000500
+#define RMBX_ACTUATION_PLANE_HOLD 0x40000600
+#define RMBX_ACTUATION_MAX_DELAY 64
+
+typedef struct rmbx_actuation_params {
+  float noise, bias, hold; /* S, B (normalised action units), P in [0, 1) */
+  int32_t delay, skip;     /* D env-steps; the rollout's skip (noise draw = r - r % skip) */
+} rmbx_actuation_params;
+
+int rmbx_action_perturb(const double* action, double* out, uint8_t* mask_out, double* ring,
+                        const rmbx_actuation_params* p, const double* bias_scale,
+                        const double* noise_scale, uint64_t seed, const int32_t* episode,
+                        const int32_t* r, const uint8_t* mask_in, int n, int A, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Policy-input image preprocessing, batched over envs.
  * rmbx_resize_crop_u8: src u8 [n][H][W][C] (renderer frames) -> dst [n][C][ch][cw] (f32 dtype 0 /
  * bf16 dtype 1) = (v * (1/255)) * a + b, v = cv2.resize(src, (rw, rh), INTER_LINEAR)[y0+y, x0+x];

@@ -121,6 +121,7 @@ SIGNATURES = {
     "rmbx_philox_normal": (_c_int, [ctypes.c_uint64, _c_p, _c_p, _c_int, _c_int, _c_p, _c_int, _c_int, _c_int, _c_p]),
     "rmbx_image_perturb": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_p, ctypes.c_uint64, _c_p, _c_p, _c_int, _c_p, _c_int,
                                     _c_int, _c_int, _c_p]),
+    "rmbx_action_perturb": (_c_int, [_c_p] * 7 + [ctypes.c_uint64, _c_p, _c_p, _c_p, _c_int, _c_int, _c_p]),
     "rmbx_resize_crop_u8": (_c_int, [_c_p] + [_c_int] * 10 + [ctypes.c_float, ctypes.c_float, _c_p, _c_int, _c_p]),
     "rmbx_resize_f32": (_c_int, [_c_p, _c_p] + [_c_int] * 5 + [_c_p]),
     "rmbx_pointcloud_fps": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_int, _c_d, _c_p, _c_p, _c_int, _c_int,
@@ -263,6 +264,16 @@ class PerturbParams(ctypes.Structure):
     _fields_ = [("brightness", ctypes.c_float), ("contrast", ctypes.c_float), ("gain", ctypes.c_float),
                 ("noise_sigma", ctypes.c_float), ("occ_h", ctypes.c_int32), ("occ_w", ctypes.c_int32),
                 ("mean", ctypes.c_float * 3), ("std", ctypes.c_float * 3)]
+
+
+ACTUATION_MAX_DELAY = 64  # include/rmbx.h RMBX_ACTUATION_MAX_DELAY
+
+
+class ActuationParams(ctypes.Structure):
+    """rmbx_actuation_params (include/rmbx.h)."""
+
+    _fields_ = [("noise", ctypes.c_float), ("bias", ctypes.c_float), ("hold", ctypes.c_float),
+                ("delay", ctypes.c_int32), ("skip", ctypes.c_int32)]
 
 
 assert ctypes.sizeof(PerturbParams) == 48

@@ -37,6 +37,7 @@ from ..common import episode_metrics as EM
 from ..common.data_key import DataKey, action_key_codes, state_key_codes
 from ..common.data_utils import make_meta_info
 from ..common.episode_trace import TraceWriter, parse_episodes, row_bytes, select_mask
+from ..common import actuation as ACT
 from ..common.perturb import Perturber, parse_spec
 
 
@@ -62,6 +63,9 @@ class BatchedRolloutBase:
             setattr(self.args, k, v)
         # the parsed --perturb spec (None: off); ValueError for a bad key or value
         self.perturb_spec = None if getattr(self.args, "perturb", None) is None else parse_spec(self.args.perturb)
+        # the parsed --actuation spec (None: off); ValueError for a bad key or value
+        self.actuation_spec = (None if getattr(self.args, "actuation", None) is None
+                               else ACT.parse_spec(self.args.actuation))
         torch.manual_seed(self.args.seed)
         np.random.seed(self.args.seed)
         self.device = torch.device(self.args.device)
@@ -80,6 +84,7 @@ class BatchedRolloutBase:
         self._trace = None  # the TraceWriter of a run with --trace_dir
         self._metrics = None  # the kernels.EpisodeMetrics accumulator of a run with --episode_metrics
         self._perturb = None  # the common.perturb.Perturber of a run with --perturb
+        self._actuation = None  # the common.actuation.Actuator of a run with --actuation
 
     def attach_phase_timer(self, timer):
         """Record HIP events at the policy / render / physics / glue boundaries of every env-step
@@ -173,6 +178,13 @@ class BatchedRolloutBase:
                                  "[0, 1)), noise=LEVELS (sensor noise), occluder=F (a rectangle of F x each image "
                                  "side), state_noise=S (normalised units). An episode sees the same perturbation in "
                                  "any slot, shard or re-run; info['rgb_images'], saved images and the trace stay clean")
+        parser.add_argument("--actuation", type=str, nargs="+", default=None, metavar="KEY=VALUE",
+                            help="perturb the command the robot executes, per episode and on the device (the rule: "
+                                 "include/rmbx.h, rmbx_action_perturb): noise=S bias=B (normalised action units: "
+                                 "per-inference Gaussian noise, episode-constant offset uniform in +-B), delay=D "
+                                 "(env-steps of control latency, 0..64), hold=P (probability that a step's command "
+                                 "is lost and the last one stays). An episode is actuated the same way in any slot, "
+                                 "shard or re-run; ctrl, the trace and the metrics show the executed command")
         if self.require_task_desc:
             parser.add_argument("--task_desc", type=str, required=True)
         self.set_additional_args(parser)
@@ -191,6 +203,8 @@ class BatchedRolloutBase:
         parse_episodes(self.args.trace_episodes)  # ValueError for anything but `all` or indices
         if self.args.perturb is not None:
             parse_spec(self.args.perturb)  # ValueError for a bad key or value
+        if self.args.actuation is not None:
+            ACT.parse_spec(self.args.actuation)  # ValueError for a bad key or value
         if self.args.num_episodes is not None:
             if self.args.num_episodes < 1:
                 raise ValueError("--num_episodes must be at least 1")
@@ -333,20 +347,27 @@ class BatchedRolloutBase:
         r = self.env.renderer
         self._perturb = Perturber(self.perturb_spec, self.args.seed, self.n, r.height, r.width, self.env.camera_names,
                                   self.device)
-        self._lockstep_rows = torch.arange(self.args.env_offset, self.args.env_offset + self.n, dtype=torch.int32,
-                                           device=self.device)
+        self._lockstep_rows_begin()
         print(f"[{self.__class__.__name__}] Perturb: {self.perturb_spec}", flush=True)
 
-    def _perturb_rows(self):
-        """The Perturber with the rows' (episode, draw) of the observation being made.  Lockstep: env e
-        is episode env_offset + e and every row's draw is the host's rollout_time_idx; streaming: the
-        stream's slot -> episode map and each slot's own rollout_time_idx, read from the schedule on
-        the device."""
-        pt = self._perturb
+    def _lockstep_rows_begin(self):
+        """The episodes of a lockstep run's rows: env e is episode env_offset + e."""
+        self._lockstep_rows = torch.arange(self.args.env_offset, self.args.env_offset + self.n, dtype=torch.int32,
+                                           device=self.device)
+
+    def _episode_rows(self):
+        """(episode, rollout_time_idx) of the rows at this point of the step, as set_rows of the
+        Perturber and the Actuator takes them.  Lockstep: env e is episode env_offset + e and every
+        row is at the host's rollout_time_idx (an int); streaming: the stream's slot -> episode map
+        and each slot's own rollout_time_idx, read from the schedule on the device."""
         if self.args.num_episodes is not None and getattr(self, "stream", None) is not None:
-            pt.set_rows(self.stream.slot_episode, self.sched.view(torch.int32)[:, 1])
-        else:
-            pt.set_rows(self._lockstep_rows, int(self.rollout_time_idx))
+            return self.stream.slot_episode, self.sched.view(torch.int32)[:, 1]
+        return self._lockstep_rows, int(self.rollout_time_idx)
+
+    def _perturb_rows(self):
+        """The Perturber with the rows' (episode, draw) of the observation being made (_episode_rows)."""
+        pt = self._perturb
+        pt.set_rows(*self._episode_rows())
         return pt
 
     def policy_rgb(self, cam):
@@ -375,10 +396,35 @@ class BatchedRolloutBase:
     def set_command_data(self):
         """RolloutBase.set_command_data (:496-509): the policy action routed key by key through
         MotionManager / ArmManager (joint / relative joint / gripper / eef pose / relative eef
-        pose commands, rmbx_motion_command), with is_skip = rollout_time_idx % skip != 0."""
-        is_skip = self.rollout_time_idx % self.args.skip != 0
-        K.motion_command(self._placement, self.policy_action, self._action_codes, is_skip, self._glo, self._ghi,
-                         self.q_cmd, self.grip_cmd, self._tgt_R, self._tgt_p)
+        pose commands, rmbx_motion_command), with is_skip = rollout_time_idx % skip != 0.
+        --actuation: the command that arrives at this step, under the mask of the rows it arrives for."""
+        action, is_skip, mask = self._executed_action(self.rollout_time_idx, None)
+        K.motion_command(self._placement, action, self._action_codes, is_skip, self._glo, self._ghi,
+                         self.q_cmd, self.grip_cmd, self._tgt_R, self._tgt_p, mask=mask)
+
+    # -- actuation perturbation (--actuation) ------------------------------------------------------
+    def _actuation_begin(self):
+        """The Actuator of this run, and its one printed line."""
+        self._actuation = ACT.Actuator(self.actuation_spec, self.args.seed, self.n, self.action_dim, self.args.skip,
+                                       self.action_stats(), self.device)
+        self._lockstep_rows_begin()
+        print(f"[{self.__class__.__name__}] Actuation: {self.actuation_spec}", flush=True)
+
+    def action_stats(self):
+        """The statistics denormalize_data turns the policy's output into the action with."""
+        return self.model_meta_info["action"]
+
+    def _executed_action(self, r, mask):
+        """(action, is_skip, mask) rmbx_motion_command gets at the host's rollout step r for the rows of
+        `mask` (None: all): the policy action itself, or with --actuation the command that arrives at
+        this step (rmbx_action_perturb), the is_skip of the step it was made for and the rows it
+        arrives for."""
+        act = getattr(self, "_actuation", None)
+        if act is None:
+            return self.policy_action, r % self.args.skip != 0, mask
+        act.set_rows(*self._episode_rows())
+        action, arrived = act(self.policy_action, mask_in=mask)
+        return action, act.is_skip(r), arrived
 
     def env_action(self):
         return torch.cat([self.q_cmd, self.grip_cmd], dim=1)
@@ -423,6 +469,9 @@ class BatchedRolloutBase:
         self._perturb = None
         if getattr(self, "perturb_spec", None) is not None:
             self._perturb_begin()
+        self._actuation = None
+        if getattr(self, "actuation_spec", None) is not None:
+            self._actuation_begin()
         if getattr(self.args, "trace_dir", None) and self.args.num_episodes is None:
             self._trace_begin()
         if getattr(self.args, "episode_metrics", False) and self.args.num_episodes is None:
@@ -507,6 +556,8 @@ class BatchedRolloutBase:
             header["sampler_noise"] = str(a.sampler_noise)
         if getattr(self, "perturb_spec", None) is not None:  # what Replay --as_seen applies
             header["perturb"] = self.perturb_spec.as_dict()
+        if getattr(self, "actuation_spec", None) is not None:  # how the recorded ctrl came about
+            header["actuation"] = self.actuation_spec.as_dict()
         self._trace = TraceWriter(directory, header, trace)
         # the size the run can reach: an episode ends by max_duration + the post-success second
         dt = env.frame_skip * env.sim_timestep
@@ -727,9 +778,9 @@ class BatchedRolloutBase:
             self.rollout_time_idx = hr
             if hr % skip == 0:
                 self._timed_infer()
-            K.motion_command(self._placement, self.policy_action, self._action_codes, hr % skip != 0, self._glo,
-                             self._ghi, self.q_cmd, self.grip_cmd, self._tgt_R, self._tgt_p,
-                             mask=in_rollout.to(torch.uint8))
+            action, is_skip, mask = self._executed_action(hr, in_rollout.to(torch.uint8))
+            K.motion_command(self._placement, action, self._action_codes, is_skip, self._glo, self._ghi, self.q_cmd,
+                             self.grip_cmd, self._tgt_R, self._tgt_p, mask=mask)
         # 3. step + schedule
         self.obs, self.reward, _, _, self.info = self.env.step(self.env_action(), active=self._step_mask)
         if getattr(self, "_metrics", None) is not None:
@@ -830,6 +881,8 @@ class BatchedRolloutBase:
                 self._append_metrics_result()
             if getattr(self, "perturb_spec", None) is not None:
                 self.result["perturb"] = self.perturb_spec.as_dict()
+            if getattr(self, "actuation_spec", None) is not None:
+                self.result["actuation"] = self.actuation_spec.as_dict()
         if self.args.save_last_image:
             self.save_rgb_images(v)
         if rank == 0 and self.args.result_filename is not None:
@@ -884,6 +937,8 @@ class BatchedRolloutBase:
                 self._append_metrics_result()
             if getattr(self, "perturb_spec", None) is not None:
                 self.result["perturb"] = self.perturb_spec.as_dict()
+            if getattr(self, "actuation_spec", None) is not None:
+                self.result["actuation"] = self.actuation_spec.as_dict()
             if self.args.result_filename is not None:
                 print(f"[{self.__class__.__name__}] Save the rollout results: {self.args.result_filename}")
                 with open(self.args.result_filename, "w") as f:

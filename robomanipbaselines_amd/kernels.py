@@ -842,6 +842,50 @@ def image_perturb(rgb, seed, episode, draw, camera, brightness=0.0, contrast=0.0
 
 
 # ------------------------------------------------------------------------------------------
+# Per-episode perturbation of the executed command (--actuation)
+# ------------------------------------------------------------------------------------------
+def action_perturb(action, seed, episode, r, ring, bias_scale, noise_scale, out, mask_out, noise=0.0, bias=0.0,
+                   delay=0, hold=0.0, skip=1, mask_in=None):
+    """One env-step of the actuation rule of include/rmbx.h (rmbx_action_perturb).
+
+    action f64 [n, A] (the policy's denormalised action); episode, r i32 [n] (r: the row's own
+    rollout_time_idx); ring f64 [n, delay + 1, A], owned by the caller and carried from step to step;
+    bias_scale, noise_scale f64 [A] (strength x the denormalisation scale); out f64 [n, A] and
+    mask_out u8 [n]: the arriving command and the rows it arrives for (rows with 0 are not written),
+    the action and mask of motion_command.  mask_in u8 [n]: rows with 0 write nothing and get
+    mask_out 0.  Shapes and dtypes are checked before the device.  Returns (out, mask_out)."""
+    seed = int(seed)
+    if not 0 <= seed < 2**64:
+        raise ValueError(f"seed must be an unsigned 64-bit value (got {seed})")
+    _chk(action, torch.float64, name="action")
+    if action.dim() != 2 or action.shape[0] < 1 or action.shape[1] < 1:
+        raise ValueError(f"action must have shape [n, A], n, A >= 1 (got {tuple(action.shape)})")
+    n, A = (int(v) for v in action.shape)
+    delay, skip = int(delay), int(skip)
+    if not 0 <= delay <= N.ACTUATION_MAX_DELAY:
+        raise ValueError(f"delay must lie in [0, {N.ACTUATION_MAX_DELAY}] (got {delay})")
+    if skip < 1:
+        raise ValueError(f"skip must be at least 1 (got {skip})")
+    _chk(episode, torch.int32, (n,), "episode")
+    _chk(r, torch.int32, (n,), "r")
+    _chk(ring, torch.float64, (n, delay + 1, A), "ring")
+    _chk(bias_scale, torch.float64, (A,), "bias_scale")
+    _chk(noise_scale, torch.float64, (A,), "noise_scale")
+    _chk(out, torch.float64, (n, A), "out")
+    _chk(mask_out, torch.uint8, (n,), "mask_out")
+    if mask_in is not None:
+        _chk(mask_in, torch.uint8, (n,), "mask_in")
+    for t, name in ((episode, "episode"), (r, "r"), (ring, "ring"), (bias_scale, "bias_scale"),
+                    (noise_scale, "noise_scale"), (out, "out"), (mask_out, "mask_out"), (mask_in, "mask_in")):
+        if t is not None and t.device != action.device:
+            raise ValueError(f"{name} is on {t.device}, action on {action.device}")
+    p = N.ActuationParams(float(noise), float(bias), float(hold), delay, skip)
+    N.call("rmbx_action_perturb", N.ptr(action), N.ptr(out), N.ptr(mask_out), N.ptr(ring), ctypes.byref(p),
+           N.ptr(bias_scale), N.ptr(noise_scale), seed, N.ptr(episode), N.ptr(r), N.ptr(mask_in), n, A, N.stream_ptr())
+    return out, mask_out
+
+
+# ------------------------------------------------------------------------------------------
 # Point-cloud observation (3D diffusion policy)
 # ------------------------------------------------------------------------------------------
 def focal_scaling(fovy_deg, height):

@@ -92,6 +92,9 @@ class RolloutSarnn(BatchedRolloutBase):
         torch.backends.cuda.matmul.allow_tf32 = False
         self.policy = self.policy.eval().requires_grad_(False).to(device=self.device, dtype=torch.float32)
 
+    def action_stats(self):
+        return self.model_meta_info["state"]  # the predicted state is the command
+
     def reset_variables(self):
         hd = self.policy.lstm_hidden_dim
         self.h = torch.zeros((self.n, hd), dtype=torch.float32, device=self.device)

@@ -66,6 +66,8 @@ def parse_args(argv=None):
                    help="accumulate the per-episode metrics every env-step (Rollout.py --episode_metrics): its cost")
     p.add_argument("--perturb", type=str, nargs="+", default=None, metavar="KEY=VALUE",
                    help="perturb the policy's observation per episode (Rollout.py --perturb): its cost")
+    p.add_argument("--actuation", type=str, nargs="+", default=None, metavar="KEY=VALUE",
+                   help="perturb the executed command per episode (Rollout.py --actuation): its cost")
     a = p.parse_args(argv)
     if a.sampler_noise is not None and not a.policy.startswith("DiffusionPolicy"):
         p.error("--sampler_noise is a flag of the diffusion policies")
@@ -81,7 +83,8 @@ def rollout_argv(a):
              "--shadows", a.shadows, "--offsamples", a.offsamples] + (["--tactile"] if a.tactile else [])
             + (["--sampler_noise", a.sampler_noise] if a.sampler_noise else [])
             + (["--episode_metrics"] if a.episode_metrics else [])
-            + (["--perturb", *a.perturb] if a.perturb else []))
+            + (["--perturb", *a.perturb] if a.perturb else [])
+            + (["--actuation", *a.actuation] if a.actuation else []))
 
 
 def main():
@@ -144,6 +147,7 @@ def main():
                       "tactile": "synthetic, every env-step" if a.tactile else None, "shadows": a.shadows,
                       "offsamples": a.offsamples, "sampler_noise": a.sampler_noise,
                       "episode_metrics": bool(a.episode_metrics), "perturb": a.perturb,
+                      "actuation": a.actuation,
                       "data": "synthetic (random-init weights)"}), flush=True)
 
 
