@@ -495,6 +495,65 @@ int rmbx_engine_forward(rmbx_engine* eng, const uint8_t* active, void* stream);
 int rmbx_engine_step_profiled(rmbx_engine* eng, int nsub, uint64_t* stage_cycles, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Per-episode randomisation of the world's physical constants (opt-in, --dynamics): contact
+ * friction, the joint damping and the mass of the objects, and the servo gain.  Where --perturb
+ * changes what the policy reads and --actuation what the robot executes, this changes the world
+ * the episode runs in.  Each env reads a row of four f64 scale factors at the few places where
+ * these model constants enter the two physics kernels; the rows are drawn on the device by a rule
+ * keyed like the other two, so that an episode meets the same world in any slot, slot count,
+ * shard or re-run.
+ *
+ * The rule, for a row with episode i32: the Philox4x32-10 rule of rmbx_philox_normal, key = seed,
+ * counter (block 0, plane RMBX_DYNAMICS_PLANE, draw 0, episode); u(w) = ((w >> 9) + 0.5) * 2^-23,
+ * exact in f32, inside (0, 1).  The plane lies above those of rmbx_action_perturb.  The strengths
+ * F (friction), D (damping), M (mass), G (gain) are f32 in [0, 1).  With S_k the k-th of them and
+ * w_k word k of the block,
+ *   scale[row][k] = 1.0 + (double)S_k * (double)(2 * u(w_k) - 1)
+ * where the bracket is f32, as the symmetric uniforms of the other two rules are; f64 otherwise, no
+ * contraction, each operation rounded once (numpy reproduces the bits).  S_k == 0 gives exactly 1.0
+ * without a draw.  The result lies in (1 - S_k, 1 + S_k): positive and finite.
+ *
+ * What scale[e][0..3] means for env e.  The scaled constant is one f64 multiply of the model's
+ * value, used exactly where the model's value is used otherwise:
+ *   0 friction  con_mu = pair_friction[3 p] * s0 for every contact pair p
+ *   1 damping   dof_damping[k] * s1 for the dofs of object bodies, in qfrc_passive and in the
+ *               implicitfast matrix
+ *   2 mass      body_mass[b] * s2 and body_inertia[b][0..8] * s2 for object bodies.
+ *               body_invweight0, dof_invweight0 and meaninertia stay the model's: what editing an
+ *               mjModel in place without mj_setConst gives
+ *   3 gain      act_gain[u] * s3, act_bias[3u + 1] * s3 and act_bias[3u + 2] * s3 for every
+ *               actuator (kp and kv of a position servo); act_bias[3u], the control range and the
+ *               force range are untouched.  The kv part of the implicitfast matrix scales with it
+ * Object bodies are those with body_group[b] != 0; the rollout marks every body other than the
+ * world whose body_rootid differs from that of the body carrying the first arm joint.
+ * A component that is exactly 1.0 leaves its quantity's bits unchanged, and a row of all ones is
+ * bit for bit a row of an engine with nothing bound: with s1 == 1 and s3 == 1 the implicitfast
+ * addition to M is the constant built at create, otherwise
+ * h * (damping_r * [s1 for an object dof] + (s3 * kv-sum)_{r c}) per matrix entry.
+ *
+ * rmbx_dynamics_draw: scale f64 [n][4] from episode i32 [n]; one launch, one thread per row, no
+ * host synchronisation.  A row with active[row] == 0 is not written (active NULL = every row).
+ * Episode -1 (a retired slot) is no special case: it is counter word 0xffffffff.  n >= 1, every
+ * strength in [0, 1), no NULL pointer but active (RMBX_ERR_ARG otherwise, before the launch).
+ *
+ * rmbx_engine_bind_dynamics: scale is device f64 [n_env][4], caller-owned, and is read by every
+ * later launch of the engine (step, its redo pass, forward), once per block; body_group is host u8
+ * [nbody], copied at the call.  scale == NULL unbinds (body_group is then ignored): the engine
+ * launches the same kernels as one that never had scales bound.  Setup, not hot path: it may
+ * allocate and synchronise.  Scales a caller makes itself must be finite and positive; nothing on
+ * the device checks them.
+ * ------------------------------------------------------------------------------------------- */
+#define RMBX_DYNAMICS_PLANE 0x40000700
+
+typedef struct rmbx_dynamics_params {
+  float friction, damping, mass, gain; /* F, D, M, G in [0, 1) */
+} rmbx_dynamics_params;
+
+int rmbx_dynamics_draw(uint64_t seed, const int32_t* episode, const rmbx_dynamics_params* p, double* scale,
+                       const uint8_t* active, int n, void* stream);
+int rmbx_engine_bind_dynamics(rmbx_engine* eng, const double* scale, const uint8_t* body_group);
+
+/* ---------------------------------------------------------------------------------------------
  * Arm command: batched FK and damped-least-squares IK steps (reach phases).
  * Replaces common/body/ArmManager.py:213-218 (forward_kinematics) and :220-243
  * (inverse_kinematics, one iteration per call in the reference; n_iter here) with the Pinocchio

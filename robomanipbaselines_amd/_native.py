@@ -54,6 +54,8 @@ SIGNATURES = {
     "rmbx_engine_step": (_c_int, [_c_p, _c_int, _c_p, _c_p]),
     "rmbx_engine_forward": (_c_int, [_c_p, _c_p, _c_p]),
     "rmbx_engine_step_profiled": (_c_int, [_c_p, _c_int, _c_p, _c_p]),
+    "rmbx_dynamics_draw": (_c_int, [ctypes.c_uint64, _c_p, _c_p, _c_p, _c_p, _c_int, _c_p]),
+    "rmbx_engine_bind_dynamics": (_c_int, [_c_p, _c_p, _c_p]),
     "rmbx_arm_ik": (_c_int, [_c_p] * 5 + [_c_int, _c_int, _c_p]),
     "rmbx_arm_fk": (_c_int, [_c_p] * 4 + [_c_int, _c_p]),
     "rmbx_motion_state": (_c_int, [_c_p] * 9 + [_c_int, _c_p, _c_int, _c_int, _c_p]),
@@ -275,6 +277,15 @@ class ActuationParams(ctypes.Structure):
     _fields_ = [("noise", ctypes.c_float), ("bias", ctypes.c_float), ("hold", ctypes.c_float),
                 ("delay", ctypes.c_int32), ("skip", ctypes.c_int32)]
 
+
+class DynamicsParams(ctypes.Structure):
+    """rmbx_dynamics_params (include/rmbx.h)."""
+
+    _fields_ = [("friction", ctypes.c_float), ("damping", ctypes.c_float), ("mass", ctypes.c_float),
+                ("gain", ctypes.c_float)]
+
+
+DYNAMICS_PLANE = 0x40000700  # include/rmbx.h RMBX_DYNAMICS_PLANE
 
 assert ctypes.sizeof(PerturbParams) == 48
 # include/rmbx.h RMBX_PERTURB_PLANE_*

@@ -38,6 +38,7 @@ from ..common.data_key import DataKey, action_key_codes, state_key_codes
 from ..common.data_utils import make_meta_info
 from ..common.episode_trace import TraceWriter, parse_episodes, row_bytes, select_mask
 from ..common import actuation as ACT
+from ..common import dynamics as DYN
 from ..common.perturb import Perturber, parse_spec
 
 
@@ -66,6 +67,9 @@ class BatchedRolloutBase:
         # the parsed --actuation spec (None: off); ValueError for a bad key or value
         self.actuation_spec = (None if getattr(self.args, "actuation", None) is None
                                else ACT.parse_spec(self.args.actuation))
+        # the parsed --dynamics spec (None: off); ValueError for a bad key or value
+        self.dynamics_spec = (None if getattr(self.args, "dynamics", None) is None
+                              else DYN.parse_spec(self.args.dynamics))
         torch.manual_seed(self.args.seed)
         np.random.seed(self.args.seed)
         self.device = torch.device(self.args.device)
@@ -85,6 +89,7 @@ class BatchedRolloutBase:
         self._metrics = None  # the kernels.EpisodeMetrics accumulator of a run with --episode_metrics
         self._perturb = None  # the common.perturb.Perturber of a run with --perturb
         self._actuation = None  # the common.actuation.Actuator of a run with --actuation
+        self._dynamics = None  # the common.dynamics.Dynamics of a run with --dynamics
 
     def attach_phase_timer(self, timer):
         """Record HIP events at the policy / render / physics / glue boundaries of every env-step
@@ -185,6 +190,13 @@ class BatchedRolloutBase:
                                  "(env-steps of control latency, 0..64), hold=P (probability that a step's command "
                                  "is lost and the last one stays). An episode is actuated the same way in any slot, "
                                  "shard or re-run; ctrl, the trace and the metrics show the executed command")
+        parser.add_argument("--dynamics", type=str, nargs="+", default=None, metavar="KEY=VALUE",
+                            help="randomise the world's physical constants per episode, on the device (the rule: "
+                                 "include/rmbx.h, rmbx_dynamics_draw): friction=F damping=D mass=M gain=G, each in "
+                                 "[0, 1): the contact friction, the objects' joint damping, the objects' mass and "
+                                 "inertia, and the servo gains (kp, kv) are multiplied by a factor uniform in "
+                                 "(1 - S, 1 + S). An episode meets the same world in any slot, shard or re-run; "
+                                 "common.dynamics.scales(seed, episodes, spec) gives the factors on the host")
         if self.require_task_desc:
             parser.add_argument("--task_desc", type=str, required=True)
         self.set_additional_args(parser)
@@ -205,6 +217,8 @@ class BatchedRolloutBase:
             parse_spec(self.args.perturb)  # ValueError for a bad key or value
         if self.args.actuation is not None:
             ACT.parse_spec(self.args.actuation)  # ValueError for a bad key or value
+        if self.args.dynamics is not None:
+            DYN.parse_spec(self.args.dynamics)  # ValueError for a bad key or value
         if self.args.num_episodes is not None:
             if self.args.num_episodes < 1:
                 raise ValueError("--num_episodes must be at least 1")
@@ -410,6 +424,21 @@ class BatchedRolloutBase:
         self._lockstep_rows_begin()
         print(f"[{self.__class__.__name__}] Actuation: {self.actuation_spec}", flush=True)
 
+    # -- dynamics randomisation (--dynamics) ---------------------------------------------------------
+    def _dynamics_begin(self):
+        """The Dynamics of this run (made once: it binds its scale rows to the engine), the draw of
+        the lockstep rows' episodes -- before env.reset runs its forward pass -- and its one printed
+        line."""
+        from ..envs.ur5e_base import ARM_JOINTS
+
+        if self._dynamics is None:
+            eng = self.env.engine
+            self._dynamics = DYN.Dynamics(self.dynamics_spec, self.args.seed, eng,
+                                          DYN.object_bodies(eng.arrays, ARM_JOINTS[0]), self.device)
+        self._lockstep_rows_begin()
+        self._dynamics.draw(self._lockstep_rows)
+        print(f"[{self.__class__.__name__}] Dynamics: {self.dynamics_spec}", flush=True)
+
     def action_stats(self):
         """The statistics denormalize_data turns the policy's output into the action with."""
         return self.model_meta_info["action"]
@@ -450,6 +479,8 @@ class BatchedRolloutBase:
         world = np.array([wl[(g0 + e) % len(wl)] for e in range(self.n)])
         self.env.world_random_scale = self.args.world_random_scale
         self.world_idx = self.env.modify_world(world_idx=world)
+        if getattr(self, "dynamics_spec", None) is not None:
+            self._dynamics_begin()
         self.obs, self.info = self.env.reset(seed=self.args.seed)
         self._bind_state_stats()
         dev = self.device
@@ -558,6 +589,8 @@ class BatchedRolloutBase:
             header["perturb"] = self.perturb_spec.as_dict()
         if getattr(self, "actuation_spec", None) is not None:  # how the recorded ctrl came about
             header["actuation"] = self.actuation_spec.as_dict()
+        if getattr(self, "dynamics_spec", None) is not None:  # the world each recorded episode ran in
+            header["dynamics"] = self.dynamics_spec.as_dict()
         self._trace = TraceWriter(directory, header, trace)
         # the size the run can reach: an episode ends by max_duration + the post-success second
         dt = env.frame_skip * env.sim_timestep
@@ -795,6 +828,8 @@ class BatchedRolloutBase:
             self._mark("recycle")
             st.recycle()
             K.sched_active(self.sched, n_pre, out=self._step_mask)
+            if getattr(self, "_dynamics", None) is not None:  # the new episodes' worlds, before their forward pass
+                self._dynamics.draw(st.slot_episode, active=st.recycled)
             self.env.refresh(active=st.recycled)
             self.obs, self.reward, self.info = self.env._get_obs(), self.env.reward, self.env._get_info()
             self._mark("glue")
@@ -883,6 +918,8 @@ class BatchedRolloutBase:
                 self.result["perturb"] = self.perturb_spec.as_dict()
             if getattr(self, "actuation_spec", None) is not None:
                 self.result["actuation"] = self.actuation_spec.as_dict()
+            if getattr(self, "dynamics_spec", None) is not None:
+                self.result["dynamics"] = self.dynamics_spec.as_dict()
         if self.args.save_last_image:
             self.save_rgb_images(v)
         if rank == 0 and self.args.result_filename is not None:
@@ -939,6 +976,8 @@ class BatchedRolloutBase:
                 self.result["perturb"] = self.perturb_spec.as_dict()
             if getattr(self, "actuation_spec", None) is not None:
                 self.result["actuation"] = self.actuation_spec.as_dict()
+            if getattr(self, "dynamics_spec", None) is not None:
+                self.result["dynamics"] = self.dynamics_spec.as_dict()
             if self.args.result_filename is not None:
                 print(f"[{self.__class__.__name__}] Save the rollout results: {self.args.result_filename}")
                 with open(self.args.result_filename, "w") as f:

@@ -87,6 +87,12 @@ struct rmbx_engine {
   bool bound;
   size_t front_lds;  // dynamic LDS of a front-kernel launch (front_launch_lds)
   int solver_minb;   // solver blocks per CU of this batch size (solver_minb_for)
+  // per-env scale factors of the physical constants (rmbx_engine_bind_dynamics); dyn_scale NULL:
+  // nothing bound, the launches are those of an engine that never had any
+  const double* dyn_scale;    // device [n_env][4], caller-owned
+  const uint8_t* dyn_group;   // device [nbody]: 1 = object body (mass, damping scale with the env)
+  const double* dyn_kv;       // device: the actuator velocity-gain part of hBblk / h, packed like it
+  size_t front_lds_dyn;       // front_launch_lds of the scaled front kernel
 };
 
 namespace rmbx {
@@ -110,6 +116,10 @@ struct Env {
   int32_t* stats;
   double* sh;  // front-kernel LDS: xpos, xquat, xmat, cvel, cacc, cfrc, cdofdot
   const int32_t* subtree_end;  // DFS subtree ranges (tree passes, chain membership)
+  // DYN kernels only: the env's scale factors (friction, damping, mass, gain), wave-uniform, and
+  // the object-body marks
+  double dyn[4];
+  const uint8_t* group;
 };
 
 #define W(name) (e.ws + e.L->name)
@@ -319,6 +329,7 @@ __host__ __device__ __forceinline__ size_t front_lds_doubles(int nb, int nv) { r
 #define LDS_CRB(e) (LDS_CINERT(e) + 10 * (e).m->nbody)
 #define LDS_CDOF(e) (LDS_CRB(e) + 10 * (e).m->nbody)
 
+template <bool DYN>
 __device__ void com_pos_crb(Env& e, int lane, const int32_t* subtree_end) {
   const rmbx_model& m = *e.m;
   const int nv = m.nv, nb = m.nbody;
@@ -331,14 +342,23 @@ __device__ void com_pos_crb(Env& e, int lane, const int32_t* subtree_end) {
       for (int k = 0; k < 10; k++) I[k] = 0;
       continue;
     }
-    const double mass = m.body_mass[b];
+    double mass = m.body_mass[b];
     const double* c = W(xipos) + 3 * b;
     const double* R = e.sh + 7 * nb + 9 * b;  // xmat (LDS)
     const double* Ib = m.body_inertia + 9 * b;
     double T[9], Iw[9], Rt[9];
     for (int i = 0; i < 3; i++)
       for (int j = 0; j < 3; j++) Rt[3 * i + j] = R[3 * j + i];
-    matmul3(R, Ib, T);
+    if constexpr (DYN) {
+      // an object body's mass and inertia scale with the env (x 1.0 keeps the bits)
+      const double s = e.group[b] ? e.dyn[2] : 1.0;
+      double Is[9];
+      mass = mass * s;
+      for (int i = 0; i < 9; i++) Is[i] = Ib[i] * s;
+      matmul3(R, Is, T);
+    } else {
+      matmul3(R, Ib, T);
+    }
     matmul3(T, Rt, Iw);
     const double cc = dot3(c, c);
     I[0] = mass;
@@ -504,6 +524,7 @@ __device__ void rne_backward(const rmbx_model& m, double* cfrc, const int32_t* s
   sync();
 }
 
+template <bool DYN>
 __device__ void velocity_stage(Env& e, int lane, int* s_anc, const int32_t* subtree_end) {
   const rmbx_model& m = *e.m;
   const int nv = m.nv, nb = m.nbody;
@@ -552,7 +573,9 @@ __device__ void velocity_stage(Env& e, int lane, int* s_anc, const int32_t* subt
   double* passive = W(qfrc_passive);
   for (int k = lane; k < nv; k += 64) {
     bias[k] = dot6(cdof + 6 * k, scfrc + 6 * m.dof_body[k]);
-    passive[k] = -m.dof_damping[k] * e.qvel[k];
+    double damping = m.dof_damping[k];
+    if constexpr (DYN) damping = damping * (e.group[m.dof_body[k]] ? e.dyn[1] : 1.0);
+    passive[k] = -damping * e.qvel[k];
   }
   sync();
   for (int j = lane; j < m.njnt; j += 64) {
@@ -593,7 +616,13 @@ __device__ void velocity_stage(Env& e, int lane, int* s_anc, const int32_t* subt
         vel = tv[id];
       }
       const double* bp = m.act_bias + 3 * u;
-      double f = m.act_gain[u] * c + bp[0] + bp[1] * len + bp[2] * vel;
+      double gain = m.act_gain[u], bp1 = bp[1], bp2 = bp[2];
+      if constexpr (DYN) {
+        gain = gain * e.dyn[3];
+        bp1 = bp1 * e.dyn[3];
+        bp2 = bp2 * e.dyn[3];
+      }
+      double f = gain * c + bp[0] + bp1 * len + bp2 * vel;
       if (m.act_forcelimited[u]) {
         f = f < m.act_forcerange[2 * u] ? m.act_forcerange[2 * u] : f;
         f = f > m.act_forcerange[2 * u + 1] ? m.act_forcerange[2 * u + 1] : f;
@@ -1809,7 +1838,7 @@ __device__ __forceinline__ int broadphase_runs(const Env& e, int lane, const Col
 // 2. survivors listed class-major
 // 3. one collider at a time over its class's survivors, contacts into con_tmp[survivor]
 // 4. pair-order scan of the survivors' counts, contacts copied to their final slots
-template <bool RUNS>
+template <bool RUNS, bool DYN>
 __device__ int collision(Env& e, int lane, const CollisionLds& cl, const PairRuns& pr, unsigned long long* prof) {
   const rmbx_model& m = *e.m;
   unsigned long long tp = prof ? stamp() : 0;
@@ -1920,7 +1949,10 @@ __device__ int collision(Env& e, int lane, const CollisionLds& cl, const PairRun
       for (int j = 0; j < 3; j++) W(con_pos)[3 * k + j] = t[7 * i + j];
       make_frame(t + 7 * i + 3, W(con_frame) + 9 * k);
       W(con_dist)[k] = t[7 * i + 6];
-      W(con_mu)[k] = m.pair_friction[3 * p];
+      if constexpr (DYN)
+        W(con_mu)[k] = m.pair_friction[3 * p] * e.dyn[0];
+      else
+        W(con_mu)[k] = m.pair_friction[3 * p];
       WI(con_b1)[k] = m.geom_body[m.pair_geom1[p]];
       WI(con_b2)[k] = m.geom_body[m.pair_geom2[p]];
       WI(con_condim)[k] = m.pair_condim[p];
@@ -3469,8 +3501,11 @@ __device__ void solver_sensors(Env& e, SolverShared& S, int ncon, int tree_round
   lds_sync();
 }
 
+// DYN: the env's damping (s1, object dofs) and gain (s3) scales enter the implicitfast term; kvB is
+// its actuator velocity-gain part before the factor h (rmbx_engine_bind_dynamics)
+template <bool DYN>
 __device__ void solver_integrate(Env& e, SolverShared& S, double* a, int bi, int bj, bool own,
-                                 int tid, int sub, const double* hB) {
+                                 int tid, int sub, const double* hB, const double* kvB) {
   const rmbx_model& m = *e.m;
   const int nv = m.nv, NB = (nv + 3) / 4, NVP = 4 * NB;
   const double h = m.timestep;
@@ -3479,7 +3514,23 @@ __device__ void solver_integrate(Env& e, SolverShared& S, double* a, int bi, int
     // once at create (rmbx_engine_create) in the same packed block order
     load_blockp(W(Mblk), threadIdx.x, a);
     double hb[16];
-    load_blockp(hB, threadIdx.x, hb);
+    bool scaled = false;
+    if constexpr (DYN) scaled = e.dyn[1] != 1.0 || e.dyn[3] != 1.0;  // block-uniform
+    if (scaled) {
+      // the scaled sum; an env whose two scales are exactly 1 keeps the constant's bits (else)
+      load_blockp(kvB, threadIdx.x, hb);
+#pragma unroll
+      for (int p = 0; p < 4; p++)
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          const int r = 4 * bi + p;
+          double d = 0.0;
+          if (bi == bj && p == q && r < nv) d = m.dof_damping[r] * (e.group[S.kb[r]] ? e.dyn[1] : 1.0);
+          hb[4 * p + q] = h * (d + hb[4 * p + q] * e.dyn[3]);
+        }
+    } else {
+      load_blockp(hB, threadIdx.x, hb);
+    }
 #pragma unroll
     for (int q = 0; q < 16; q++) a[q] += hb[q];
   }
@@ -3557,6 +3608,10 @@ struct KArgs {
   const double* hBblk;         // implicitfast: h * (damping + kv terms), packed like Mblk
   PairRuns runs;               // two-level broadphase (rmbx_engine::nprun > 0)
   int tree_rounds;             // pointer-jumping rounds covering the deepest body chain
+  // per-env scales of the physical constants (the DYN kernels; rmbx_engine_bind_dynamics)
+  const double* dyn_scale;     // [n_env][4] friction, damping, mass, gain
+  const uint8_t* dyn_group;    // [nbody] 1 = object body
+  const double* dyn_kv;        // implicitfast: the kv terms of hBblk before the factor h
 };
 
 
@@ -3581,6 +3636,19 @@ __device__ __forceinline__ void make_env(const KArgs& args, int env, Env& e) {
   e.sh = nullptr;
 }
 
+// The env's four scale factors, fetched once per launch: the address is the block's, so this is one
+// read for the wave, and readfirstlane keeps the values in scalar registers whichever load the
+// compiler picks.
+__device__ __forceinline__ void load_dynamics(const KArgs& args, int env, Env& e) {
+  const double* s = args.dyn_scale + 4 * (size_t)env;
+  for (int k = 0; k < 4; k++) {
+    const double v = s[k];
+    e.dyn[k] = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)),
+                                __builtin_amdgcn_readfirstlane(__double2loint(v)));
+  }
+  e.group = args.dyn_group;
+}
+
 #define PROF_BEGIN()                                        \
   unsigned long long* prof = args.prof ? args.prof + (size_t)env * RMBX_PROF_SLOTS : nullptr; \
   unsigned long long t0 = 0, t1 = 0;                        \
@@ -3598,7 +3666,9 @@ __device__ __forceinline__ void make_env(const KArgs& args, int env, Env& e) {
 // one-level kernel's register allocation).  flatten: every stage is inlined -- a stage left out of
 // line takes the Env (and through it the 1.5 KB kernel-argument block) by address, which hipcc then
 // copies to private memory per lane (the pair-run instance did: 2.4 KB of scratch per lane)
-template <bool RUNS>
+// DYN: the env's physical constants are scaled (rmbx_engine_bind_dynamics); a separate instantiation
+// for the same reason, launched only while scales are bound
+template <bool RUNS, bool DYN>
 __global__ void __launch_bounds__(64) __attribute__((flatten)) front_kernel(KArgs args) {
   extern __shared__ __attribute__((aligned(16))) double front_smem[];
   const int env = blockIdx.x;
@@ -3608,6 +3678,7 @@ __global__ void __launch_bounds__(64) __attribute__((flatten)) front_kernel(KArg
   Env e;
   make_env(args, env, e);
   if (args.redo && e.stats[3] == 0) return;
+  if constexpr (DYN) load_dynamics(args, env, e);
   // a new env-step clears the divergence-reset marker (read by the host between env-steps)
   if (args.integrate_flag && args.sub == 1 && lane == 0) e.stats[3] = 0;
   e.sh = front_smem;
@@ -3617,11 +3688,11 @@ __global__ void __launch_bounds__(64) __attribute__((flatten)) front_kernel(KArg
   kinematics(e, lane, s_anc);
   sync();
   PROF(0)
-  com_pos_crb(e, lane, args.subtree_end);
+  com_pos_crb<DYN>(e, lane, args.subtree_end);
   PROF(1)
-  velocity_stage(e, lane, s_anc, args.subtree_end);
+  velocity_stage<DYN>(e, lane, s_anc, args.subtree_end);
   PROF(2)
-  const int ncon = collision<RUNS>(e, lane, collision_lds(e, args.runs), args.runs, prof);
+  const int ncon = collision<RUNS, DYN>(e, lane, collision_lds(e, args.runs), args.runs, prof);
   sync();
   PROF(3)
   int ne = 0, nlim = 0;
@@ -3638,7 +3709,7 @@ __global__ void __launch_bounds__(64) __attribute__((flatten)) front_kernel(KArg
 }
 
 // back half: Newton solve, constraint forces, sensors, implicitfast integration (4 waves/env)
-template <int MINB>
+template <int MINB, bool DYN>
 __global__ void __launch_bounds__(SOLVER_THREADS, MINB) solver_kernel(KArgs args) {
   __shared__ SolverShared S;
   const int env = blockIdx.x;
@@ -3648,6 +3719,7 @@ __global__ void __launch_bounds__(SOLVER_THREADS, MINB) solver_kernel(KArgs args
   Env e;
   make_env(args, env, e);
   if (args.redo && e.stats[3] == 0) return;
+  if constexpr (DYN) load_dynamics(args, env, e);
   const int NB = (args.m.nv + 3) / 4;
   int bi = 0, bj = 0;
   const bool own = tid < NB * (NB + 1) / 2;
@@ -3717,7 +3789,7 @@ __global__ void __launch_bounds__(SOLVER_THREADS, MINB) solver_kernel(KArgs args
   solver_sensors(e, S, ncon, args.tree_rounds, tid);
   PROF(6)
   if (tid == 0) e.stats[2] = iters;
-  if (args.integrate_flag) solver_integrate(e, S, a, bi, bj, own, tid, args.sub, args.hBblk);
+  if (args.integrate_flag) solver_integrate<DYN>(e, S, a, bi, bj, own, tid, args.sub, args.hBblk, args.dyn_kv);
   PROF(7)
 }
 
@@ -3737,13 +3809,37 @@ static int solver_minb_for(int n_env) {
   return n_env <= 2 * cus ? 2 : 4;
 }
 
-static void launch_solver(int minb, int n_env, hipStream_t st, const KArgs& a) {
+template <bool DYN>
+static void launch_solver_v(int minb, int n_env, hipStream_t st, const KArgs& a) {
   if (minb == 2)
-    hipLaunchKernelGGL(solver_kernel<2>, dim3(n_env), dim3(SOLVER_THREADS), 0, st, a);
+    hipLaunchKernelGGL((solver_kernel<2, DYN>), dim3(n_env), dim3(SOLVER_THREADS), 0, st, a);
   else if (minb == 3)
-    hipLaunchKernelGGL(solver_kernel<3>, dim3(n_env), dim3(SOLVER_THREADS), 0, st, a);
+    hipLaunchKernelGGL((solver_kernel<3, DYN>), dim3(n_env), dim3(SOLVER_THREADS), 0, st, a);
   else
-    hipLaunchKernelGGL(solver_kernel<4>, dim3(n_env), dim3(SOLVER_THREADS), 0, st, a);
+    hipLaunchKernelGGL((solver_kernel<4, DYN>), dim3(n_env), dim3(SOLVER_THREADS), 0, st, a);
+}
+
+// the kernel variants are chosen here: with no scales bound (a.dyn_scale NULL) the launches are
+// the unscaled instantiations
+static void launch_solver(int minb, int n_env, hipStream_t st, const KArgs& a) {
+  if (a.dyn_scale)
+    launch_solver_v<true>(minb, n_env, st, a);
+  else
+    launch_solver_v<false>(minb, n_env, st, a);
+}
+
+static void launch_front(int nprun, int n_env, size_t lds, hipStream_t st, const KArgs& a) {
+  if (a.dyn_scale) {
+    if (nprun > 0)
+      hipLaunchKernelGGL((front_kernel<true, true>), dim3(n_env), dim3(64), lds, st, a);
+    else
+      hipLaunchKernelGGL((front_kernel<false, true>), dim3(n_env), dim3(64), lds, st, a);
+  } else {
+    if (nprun > 0)
+      hipLaunchKernelGGL((front_kernel<true, false>), dim3(n_env), dim3(64), lds, st, a);
+    else
+      hipLaunchKernelGGL((front_kernel<false, false>), dim3(n_env), dim3(64), lds, st, a);
+  }
 }
 
 static Layout make_layout(const rmbx_model& m) {
@@ -3837,7 +3933,7 @@ static Layout make_layout(const rmbx_model& m) {
 
 using namespace rmbx;
 
-static size_t front_launch_lds(const rmbx_engine* eng);
+static size_t front_launch_lds(const rmbx_engine* eng, bool scaled = false);
 
 // ------------------------------------------------------------------------------------------
 // C ABI
@@ -3983,20 +4079,26 @@ int rmbx_engine_create(const struct rmbx_model* model, int n_env, rmbx_engine** 
     // actuators as kv * coef_r * coef_c), the implicitfast addition to M, in packed 4x4 blocks
     const int nv = h.nv, NB = (nv + 3) / 4;
     std::vector<double> hb(16 * (size_t)(NB * (NB + 1) / 2), 0.0);
+    // the kv terms alone, before the factor h: the part an env's gain scale multiplies
+    // (rmbx_engine_bind_dynamics; solver_integrate<true>)
+    std::vector<double> kvb(hb.size(), 0.0);
     for (int bi = 0, t = 0; bi < NB; bi++)
       for (int bj = 0; bj <= bi; bj++, t++)
         for (int p = 0; p < 4; p++)
           for (int q = 0; q < 4; q++) {
             const int r = 4 * bi + p, cc = 4 * bj + q;
             if (r >= nv || cc >= nv) continue;
-            double add = 0;
+            double add = 0, kvsum = 0;
             if (r == cc) add += h.dof_damping[r];
             for (int u = 0; u < h.nu; u++) {
               const double kv = -h.act_bias[3 * u + 2];
               if (kv == 0) continue;
               const int id = h.act_trnid[u];
               if (h.act_trntype[u] == RMBX_TRN_JOINT) {
-                if (r == cc && h.jnt_dofadr[id] == r) add += kv;
+                if (r == cc && h.jnt_dofadr[id] == r) {
+                  add += kv;
+                  kvsum += kv;
+                }
               } else {
                 double cr = 0, cq = 0;
                 for (int w = h.ten_adr[id]; w < h.ten_adr[id] + h.ten_num[id]; w++) {
@@ -4005,11 +4107,14 @@ int rmbx_engine_create(const struct rmbx_model* model, int n_env, rmbx_engine** 
                   if (d == cc) cq += h.wrap_coef[w];
                 }
                 add += kv * cr * cq;
+                kvsum += kv * cr * cq;
               }
             }
             hb[16 * t + 4 * p + q] = h.timestep * add;
+            kvb[16 * t + 4 * p + q] = kvsum;
           }
     if (st == RMBX_OK) st = upload(eng, hb.data(), hb.size(), &eng->hBblk);
+    if (st == RMBX_OK) st = upload(eng, kvb.data(), kvb.size(), &eng->dyn_kv);
   }
   if (st != RMBX_OK) {
     rmbx_engine_destroy(eng);
@@ -4017,6 +4122,9 @@ int rmbx_engine_create(const struct rmbx_model* model, int n_env, rmbx_engine** 
   }
   eng->L = make_layout(h);
   eng->front_lds = front_launch_lds(eng);
+  eng->dyn_scale = nullptr;
+  eng->dyn_group = nullptr;
+  eng->front_lds_dyn = eng->front_lds;
   eng->solver_minb = solver_minb_for(n_env);
   *out = eng;
   return RMBX_OK;
@@ -4095,13 +4203,38 @@ int rmbx_engine_bind(rmbx_engine* eng, const rmbx_env_buffers* bufs) {
   return RMBX_OK;
 }
 
+int rmbx_engine_bind_dynamics(rmbx_engine* eng, const double* scale, const uint8_t* body_group) {
+  RMBX_CHECK_ARG(eng, "NULL engine");
+  if (!scale) {
+    eng->dyn_scale = nullptr;  // the unscaled kernels again; the marks stay allocated for a later bind
+    return RMBX_OK;
+  }
+  RMBX_CHECK_ARG(body_group, "rmbx_engine_bind_dynamics: body_group is NULL");
+  RMBX_CHECK_ARG((reinterpret_cast<uintptr_t>(scale) & 7u) == 0, "rmbx_engine_bind_dynamics: scale is not 8-byte aligned");
+  const size_t nb = (size_t)eng->host.nbody;
+  std::vector<uint8_t> marks(nb);
+  for (size_t b = 0; b < nb; b++) marks[b] = body_group[b] ? 1 : 0;
+  marks[0] = 0;  // the world body is never an object
+  if (!eng->dyn_group) {
+    const int st = upload(eng, marks.data(), nb, &eng->dyn_group);
+    if (st != RMBX_OK) return st;
+    eng->front_lds_dyn = front_launch_lds(eng, true);
+  } else {
+    // launches already enqueued may still read the marks: wait for them before overwriting
+    RMBX_CHECK_HIP(hipDeviceSynchronize());
+    RMBX_CHECK_HIP(hipMemcpy(const_cast<uint8_t*>(eng->dyn_group), marks.data(), nb, hipMemcpyHostToDevice));
+  }
+  eng->dyn_scale = scale;
+  return RMBX_OK;
+}
+
 // Dynamic LDS of a front-kernel launch: the model's need, padded so the n_env blocks spread
 // evenly over their rounds of blocks.  With k envs fitting a CU (LDS- or register-bound) the launch
 // takes R = ceil(n_env / (k CUs)) rounds; asking for LDS that admits only ceil(n_env / (R CUs)) per
 // CU gives every CU the same count in every round (otherwise the dispatcher may stack k on some
 // CUs and leave others short, or run a last round of a few envs alone).  RMBX_FRONT_BALANCE=0: the
 // plain need.
-static size_t front_launch_lds(const rmbx_engine* eng) {
+static size_t front_launch_lds(const rmbx_engine* eng, bool scaled) {
   const size_t need = front_kernel_lds_bytes(eng->host, eng->nprun);
   const char* be = std::getenv("RMBX_FRONT_BALANCE");
   if (be && std::atoi(be) == 0) return need;
@@ -4110,8 +4243,10 @@ static size_t front_launch_lds(const rmbx_engine* eng) {
       cus <= 0)
     return need;
   hipFuncAttributes fa{};
-  const void* fn = eng->nprun > 0 ? reinterpret_cast<const void*>(&front_kernel<true>)
-                                  : reinterpret_cast<const void*>(&front_kernel<false>);
+  const void* fn = eng->nprun > 0 ? (scaled ? reinterpret_cast<const void*>(&front_kernel<true, true>)
+                                         : reinterpret_cast<const void*>(&front_kernel<true, false>))
+                                  : (scaled ? reinterpret_cast<const void*>(&front_kernel<false, true>)
+                                         : reinterpret_cast<const void*>(&front_kernel<false, false>));
   if (hipFuncGetAttributes(&fa, fn) != hipSuccess) return need;
   const size_t cu_lds = 160 * 1024, stat = fa.sharedSizeBytes;
   const int regs = fa.numRegs > 0 ? fa.numRegs : 256;
@@ -4149,6 +4284,10 @@ static int launch(rmbx_engine* eng, int nsub, int integ, const uint8_t* active, 
   a.subtree_end = eng->subtree_end;
   a.tree_rounds = eng->tree_rounds;
   a.hBblk = eng->hBblk;
+  a.dyn_scale = eng->dyn_scale;
+  a.dyn_group = eng->dyn_group;
+  a.dyn_kv = eng->dyn_kv;
+  const size_t front_lds = eng->dyn_scale ? eng->front_lds_dyn : eng->front_lds;
   a.runs.n = eng->nprun;
   a.runs.start = eng->prun_start;
   a.runs.body = eng->prun_body;
@@ -4158,11 +4297,7 @@ static int launch(rmbx_engine* eng, int nsub, int integ, const uint8_t* active, 
   const int reps = integ ? nsub : 1;
   for (int s = 0; s < reps; s++) {
     a.sub = s + 1;
-    const size_t front_lds = eng->front_lds;
-    if (eng->nprun > 0)
-      hipLaunchKernelGGL(front_kernel<true>, dim3(eng->n_env), dim3(64), front_lds, st, a);
-    else
-      hipLaunchKernelGGL(front_kernel<false>, dim3(eng->n_env), dim3(64), front_lds, st, a);
+    launch_front(eng->nprun, eng->n_env, front_lds, st, a);
     RMBX_CHECK_LAUNCH();
     launch_solver(eng->solver_minb, eng->n_env, st, a);
     RMBX_CHECK_LAUNCH();
@@ -4173,11 +4308,7 @@ static int launch(rmbx_engine* eng, int nsub, int integ, const uint8_t* active, 
     a.sub = nsub + 1;
     a.redo = 1;
     a.prof = nullptr;
-    const size_t front_lds = eng->front_lds;
-    if (eng->nprun > 0)
-      hipLaunchKernelGGL(front_kernel<true>, dim3(eng->n_env), dim3(64), front_lds, st, a);
-    else
-      hipLaunchKernelGGL(front_kernel<false>, dim3(eng->n_env), dim3(64), front_lds, st, a);
+    launch_front(eng->nprun, eng->n_env, front_lds, st, a);
     RMBX_CHECK_LAUNCH();
     launch_solver(eng->solver_minb, eng->n_env, st, a);
     RMBX_CHECK_LAUNCH();

@@ -98,6 +98,25 @@ class PhysicsEngine:
     def forward(self, active=None):
         N.call("rmbx_engine_forward", self._h, N.ptr(active), N.stream_ptr())
 
+    def bind_dynamics(self, scale, body_group=None):
+        """Per-env scale factors of the physical constants (include/rmbx.h, rmbx_engine_bind_dynamics):
+        scale f64 [n_env, 4] on the engine's device (friction, damping, mass, gain), kept by reference
+        and read at every later step / forward -- the caller may rewrite rows between launches;
+        body_group u8 [nbody] on the host (numpy), 1 for the bodies whose mass and joint damping
+        scale.  scale=None unbinds.  Scales must be finite and positive.  Setup, not hot path."""
+        if scale is None:
+            N.call("rmbx_engine_bind_dynamics", self._h, None, None)
+            self._dyn_scale = None
+            return
+        if (not isinstance(scale, torch.Tensor) or scale.dtype != torch.float64 or tuple(scale.shape) != (self.n_env, 4)
+                or not scale.is_contiguous() or scale.device != self.qpos.device):
+            raise ValueError(f"scale must be a contiguous f64 tensor of shape ({self.n_env}, 4) on {self.qpos.device}")
+        group = np.ascontiguousarray(body_group, dtype=np.uint8)
+        if group.shape != (self.nbody,):
+            raise ValueError(f"body_group must have shape ({self.nbody},) (got {group.shape})")
+        N.call("rmbx_engine_bind_dynamics", self._h, N.ptr(scale), N.ptr(group))
+        self._dyn_scale = scale  # keeps the bound tensor alive
+
     def _off(self, name):
         off, cnt = ctypes.c_size_t(), ctypes.c_size_t()
         N.call("rmbx_engine_ws_offset", self._h, name.encode(), ctypes.byref(off), ctypes.byref(cnt))

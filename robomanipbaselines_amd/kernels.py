@@ -886,6 +886,32 @@ def action_perturb(action, seed, episode, r, ring, bias_scale, noise_scale, out,
 
 
 # ------------------------------------------------------------------------------------------
+# Per-episode scale factors of the physical constants (--dynamics)
+# ------------------------------------------------------------------------------------------
+def dynamics_draw(seed, episode, scale, friction=0.0, damping=0.0, mass=0.0, gain=0.0, active=None):
+    """The scale rows of include/rmbx.h (rmbx_dynamics_draw): scale f64 [n, 4] (friction, damping,
+    mass, gain) of the rows' episodes i32 [n], written in place; a row with active u8 [n] == 0 is not
+    written.  The strengths are the f32 values the kernel reads, each in [0, 1).  Shapes and dtypes
+    are checked before the device.  Returns scale."""
+    seed = int(seed)
+    if not 0 <= seed < 2**64:
+        raise ValueError(f"seed must be an unsigned 64-bit value (got {seed})")
+    _chk(episode, torch.int32, name="episode")
+    if episode.dim() != 1 or episode.shape[0] < 1:
+        raise ValueError(f"episode must have shape [n], n >= 1 (got {tuple(episode.shape)})")
+    n = int(episode.shape[0])
+    _chk(scale, torch.float64, (n, 4), "scale")
+    if active is not None:
+        _chk(active, torch.uint8, (n,), "active")
+    for t, name in ((scale, "scale"), (active, "active")):
+        if t is not None and t.device != episode.device:
+            raise ValueError(f"{name} is on {t.device}, episode on {episode.device}")
+    p = N.DynamicsParams(float(friction), float(damping), float(mass), float(gain))
+    N.call("rmbx_dynamics_draw", seed, N.ptr(episode), ctypes.byref(p), N.ptr(scale), N.ptr(active), n, N.stream_ptr())
+    return scale
+
+
+# ------------------------------------------------------------------------------------------
 # Point-cloud observation (3D diffusion policy)
 # ------------------------------------------------------------------------------------------
 def focal_scaling(fovy_deg, height):

@@ -68,6 +68,8 @@ def parse_args(argv=None):
                    help="perturb the policy's observation per episode (Rollout.py --perturb): its cost")
     p.add_argument("--actuation", type=str, nargs="+", default=None, metavar="KEY=VALUE",
                    help="perturb the executed command per episode (Rollout.py --actuation): its cost")
+    p.add_argument("--dynamics", type=str, nargs="+", default=None, metavar="KEY=VALUE",
+                   help="randomise the world's physical constants per episode (Rollout.py --dynamics): its cost")
     a = p.parse_args(argv)
     if a.sampler_noise is not None and not a.policy.startswith("DiffusionPolicy"):
         p.error("--sampler_noise is a flag of the diffusion policies")
@@ -84,7 +86,8 @@ def rollout_argv(a):
             + (["--sampler_noise", a.sampler_noise] if a.sampler_noise else [])
             + (["--episode_metrics"] if a.episode_metrics else [])
             + (["--perturb", *a.perturb] if a.perturb else [])
-            + (["--actuation", *a.actuation] if a.actuation else []))
+            + (["--actuation", *a.actuation] if a.actuation else [])
+            + (["--dynamics", *a.dynamics] if a.dynamics else []))
 
 
 def main():
@@ -147,7 +150,7 @@ def main():
                       "tactile": "synthetic, every env-step" if a.tactile else None, "shadows": a.shadows,
                       "offsamples": a.offsamples, "sampler_noise": a.sampler_noise,
                       "episode_metrics": bool(a.episode_metrics), "perturb": a.perturb,
-                      "actuation": a.actuation,
+                      "actuation": a.actuation, "dynamics": a.dynamics,
                       "data": "synthetic (random-init weights)"}), flush=True)
 
 
