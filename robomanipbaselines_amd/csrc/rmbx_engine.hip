@@ -1094,6 +1094,45 @@ __device__ int col_plane(const double* cp, const double* Rp, int tb, const doubl
 #define MPR_TOLERANCE 1e-6
 #define MPR_ITERATIONS 50
 
+// "The same operation order" includes the rounding of every product: the section is compiled without
+// floating-point contraction, as the oracle (and libccd) is.  The portal tests compare against exact
+// zeros, and where the geometry is axis-aligned (a hull vertex on a box face, a finger on a cabinet
+// panel) the oracle's products cancel exactly; a fused multiply-add keeps the residue, which sent
+// the refinement to another portal (a 2.6 mm different depth on a cabinet panel) and tilted the
+// normals of shallow resting contacts by 1e-12 (tests/test_contacts_gpu.py).  The namespace holds
+// uncontracted copies of the rmbx_math.h helpers the section calls; they hide the contracted ones.
+#pragma clang fp contract(off)
+namespace mpr {
+
+__device__ __forceinline__ void matvec3(const double* R, const double* v, double* r) {
+  const double t0 = R[0] * v[0] + R[1] * v[1] + R[2] * v[2];
+  const double t1 = R[3] * v[0] + R[4] * v[1] + R[5] * v[2];
+  const double t2 = R[6] * v[0] + R[7] * v[1] + R[8] * v[2];
+  r[0] = t0;
+  r[1] = t1;
+  r[2] = t2;
+}
+__device__ __forceinline__ void mattvec3(const double* R, const double* v, double* r) {
+  const double t0 = R[0] * v[0] + R[3] * v[1] + R[6] * v[2];
+  const double t1 = R[1] * v[0] + R[4] * v[1] + R[7] * v[2];
+  const double t2 = R[2] * v[0] + R[5] * v[1] + R[8] * v[2];
+  r[0] = t0;
+  r[1] = t1;
+  r[2] = t2;
+}
+__device__ __forceinline__ void cross3(const double* a, const double* b, double* r) {
+  const double t0 = a[1] * b[2] - a[2] * b[1];
+  const double t1 = a[2] * b[0] - a[0] * b[2];
+  const double t2 = a[0] * b[1] - a[1] * b[0];
+  r[0] = t0;
+  r[1] = t1;
+  r[2] = t2;
+}
+__device__ __forceinline__ double dot3(const double* a, const double* b) {
+  return a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
+}
+__device__ __forceinline__ double norm3(const double* a) { return sqrt(dot3(a, a)); }
+
 struct ConvexObj {
   const double *c, *R, *s, *hv;
   int type, nhv;
@@ -1434,6 +1473,13 @@ __device__ int col_convex(const Env& e, int ga, int gb, double margin, Contact* 
   out->dist = dist;
   return 1;
 }
+
+}  // namespace mpr
+// Back to the build's setting for the rest of the file: build.py passes no -ffp-contract, and hipcc's
+// default for device code is fast (honouring pragmas).  If build.py ever sets the flag, set this
+// line to match it.
+#pragma clang fp contract(fast)
+using mpr::col_convex;
 
 // stable top-4 of a candidate stream by contact_deeper (earlier candidates win ties)
 __device__ void top4_insert(Contact* best, int* nb, const Contact& c) {

@@ -23,6 +23,7 @@ DEV = "cuda:0"
 
 
 def test_cabinet_engine_matches_oracle():
+    """The scene with its task contacts live, contact by contact: tests/test_contacts_gpu.py."""
     arrays = MD.load("ur5e_cabinet")
     info = MD.ModelInfo(arrays)
     hq, sq = info.qposadr("hinge"), info.qposadr("slide")

@@ -20,6 +20,7 @@ DEV = "cuda:0"
 
 
 def test_door_engine_matches_oracle():
+    """The scene with its task contacts live, contact by contact: tests/test_contacts_gpu.py."""
     arrays = MD.load("ur5e_door")
     rng = np.random.default_rng(3)
     states = []

@@ -45,6 +45,7 @@ def _load(eng, states):
 
 
 def test_insert_engine_matches_oracle():
+    """The scene with its task contacts live, contact by contact: tests/test_contacts_gpu.py."""
     arrays = MD.load("ur5e_insert")
     states = _states(arrays, 4)
     eng = PhysicsEngine(arrays, len(states), DEV)

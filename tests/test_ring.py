@@ -78,6 +78,7 @@ def test_ring_hangs_on_the_hooks_in_the_oracle(arrays):
 
 @pytest.mark.gpu
 def test_ring_engine_matches_oracle(arrays):
+    """The scene with its task contacts live, contact by contact: tests/test_contacts_gpu.py."""
     import torch
 
     from oracle.dyn import OracleEnv

@@ -23,6 +23,7 @@ DEV = "cuda:0"
 
 
 def test_toolbox_engine_matches_oracle():
+    """The scene with its task contacts live, contact by contact: tests/test_contacts_gpu.py."""
     arrays = MD.load("ur5e_toolbox")
     fq = MD.ModelInfo(arrays).qposadr("toolbox_freejoint")
     rng = np.random.default_rng(5)
