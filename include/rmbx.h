@@ -746,6 +746,10 @@ typedef struct rmbx_scene_tables {
    * used, and left empty, by every pass.  A 4-sample rmbx_render_scene_cached ignores the cache. */
   uint32_t* samp;
   int32_t samples;
+  /* Camera jitter (optional; NULL, what a zeroed tail gives: every env renders with *cam, every output
+   * as before): the rows f64 [n_env][8] of the camera being rendered, one per env (the rule:
+   * rmbx_camera_jitter_draw below).  Device memory, 8-byte aligned, read by every kernel of the call. */
+  const double* cam_rows;
 } rmbx_scene_tables;
 #define RMBX_SAMPLE_PATTERN {{0.375f, 0.125f}, {0.875f, 0.375f}, {0.125f, 0.625f}, {0.625f, 0.875f}}
 #define RMBX_TEX_LEVELS 16 /* mip levels per texture (images up to 32768 texels wide) */
@@ -763,7 +767,9 @@ int rmbx_render_scene(const rmbx_camera* cam, const rmbx_scene_tables* scene, co
  * aligned) = (its camera depth bits, 8-bit rgb | primitive << 24; primitive 0xff: none) is rebuilt
  * for an env whenever the camera body's pose or a static primitive's pose differs from the snapshot
  * snap f64 [n_env][7 + 12 nstatic] (caller-initialised to NaN: the first call builds every cache)
- * it was built from; dirty u8 [n_env] is workspace.  Each call then casts only the other primitives
+ * it was built from (with scene->cam_rows bound the env's row follows the poses: f64 [n_env][15 + 12
+ * nstatic], and a changed row rebuilds the env's cache); dirty u8 [n_env] is workspace.  Each call
+ * then casts only the other primitives
  * and the meshes against the cached depth and primitive (the same nearest-hit order: meshes keep
  * ties, primitives by index), so every output (rgb, depth, hit_geom, policy) equals
  * rmbx_render_scene's, which is this call with cache NULL.  RMBX_RENDER_CACHE=0 ignores the
@@ -782,6 +788,76 @@ int rmbx_render_scene_cached(const rmbx_camera* cam, const rmbx_scene_tables* sc
                              int nbody, uint8_t* rgb, float* depth, int32_t* hit_geom, void* policy_img,
                              int policy_dtype, const uint8_t* active, int n_env,
                              const rmbx_render_cache* cache, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Per-episode jitter of each camera's pose and field of view (opt-in, --camera_jitter).  Where
+ * --perturb changes the finished 8-bit frame, this moves the camera itself, so parallax, occlusion
+ * and a hand camera's view of the gripper change with it: the mount shift, tilt and lens spread
+ * between the demonstrations' camera and the deployment's.  Each env renders a camera with its own
+ * row; the rows are drawn on the device by a rule keyed by (seed, episode) like the other
+ * randomisations, so that an episode sees the same cameras in any slot, slot count, shard or re-run.
+ *
+ * A row is 8 f64: (dx, dy, dz, qw, qx, qy, qz, s).  d displaces the camera in the frame of the body
+ * it is mounted on (metres), q is a unit quaternion that rotates the camera about its own axes, s
+ * scales fovy.  The identity row is (0, 0, 0, 1, 0, 0, 0, 1).  Rows live in a device tensor f64
+ * [ncam][n][8] (camera c = its position in the scene's camera list), so one camera's rows are the
+ * contiguous [n][8] block rmbx_scene_tables.cam_rows takes.
+ *
+ * What env e renders with, given its row (cam = *cam of the call; f64, no contraction, each
+ * operation rounded once, the sums left to right as written):
+ *   pos'[k] = cam.pos[k] + d[k]
+ *   quat'   = cam.quat (x) q, the Hamilton product, with a = cam.quat, b = q:
+ *     w = a0 b0 - a1 b1 - a2 b2 - a3 b3
+ *     x = a0 b1 + a1 b0 + a2 b3 - a3 b2
+ *     y = a0 b2 - a1 b3 + a2 b0 + a3 b1
+ *     z = a0 b3 + a1 b2 - a2 b1 + a3 b0
+ *   fovy'   = (float)((double)cam.fovy_deg * s)
+ * and everything that derives from the camera (its world pose, the rays' slopes tan(fovy' / 2), the
+ * culling bounds, the texture footprint, shadows and samples) uses these values: env e is bit for bit
+ * an env of a call without rows whose *cam holds pos', quat' and fovy'.  An identity row leaves the
+ * three bitwise what they were (x + 0, x * 1 and a0 * 1 - a1 * 0 - ... are exact).  For a camera on a
+ * moving body (the hand camera) the body frame is that body's, so the rule is the same.  The static-
+ * background cache snapshots the env's row with the poses (snap is then f64 [n_env][15 + 12 nstatic]
+ * per env: the caller sizes it for the larger form when it binds rows), so a slot recycled into an
+ * episode with another row rebuilds its cache and a slot that continues does not.
+ *
+ * The draw, for camera c and a row with episode i32: the Philox4x32-10 rule of rmbx_philox_normal,
+ * key = seed, counter (block, plane RMBX_CAMERA_JITTER_PLANE, draw 0, episode); u(w) = ((w >> 9) +
+ * 0.5) * 2^-23.  With sym(w) = 2 u(w) - 1 in f32 and w_k word k of the block:
+ *   block 2c,     words 0-2: d_k = (double)P * (double)sym(w_k)           P = pos, metres
+ *   block 2c,     word 3:    s   = 1.0 + (double)F * (double)sym(w_3)     F = fovy, relative
+ *   block 2c + 1, words 0-2: r_k = (double)T * (double)sym(w_k)           T = tan_half_rot
+ *                            q   = (1, r_0, r_1, r_2) / sqrt(1 + (r_0 r_0 + r_1 r_1 + r_2 r_2))
+ * r is the rotation's Rodrigues vector (axis times the tangent of half the angle), so no sine or
+ * cosine is evaluated on the device: products, sums (|r|^2 = r_0 r_0 + r_1 r_1, then + r_2 r_2; then
+ * 1 + |r|^2), one f64 square root and four divisions, each correctly rounded (the build has no
+ * fast-math flag), no contraction: numpy reproduces the bits.  The small terms are summed before the
+ * 1 so that only one rounding of the sum happens at the size of 1: | |q| - 1 | then stays within an
+ * ulp of 1.0 (2^-52; the roundings that remain -- that sum halved by the root, the root, 1 / root --
+ * add up to 0.25 + 0.5 + 0.25 ulp at worst plus terms below 0.1; 0.99 ulp at most over 1.8 million
+ * drawn rows), where adding the squares to 1 one by one left up to 1.4.  T is f32 and the host computes it as
+ * (float)tan(radians(R) / 2) from the rot strength R in degrees; per axis the angle is below R, the
+ * whole rotation below sqrt(3) R.  A strength of zero gives its identity components exactly, without
+ * a draw.  qw > 0, |d_k| < P, |r_k| < T, s in (1 - F, 1 + F).
+ *
+ * rmbx_camera_jitter_draw: rows f64 [ncam][n][8] from episode i32 [n]; one launch, one thread per
+ * (camera, row), no host synchronisation.  A row with active[row] == 0 is not written for any camera
+ * (active NULL = every row).  Episode -1 (a retired slot) is counter word 0xffffffff.  n >= 1, ncam
+ * in [1, RMBX_CAMERA_JITTER_MAX_CAMERAS], pos in [0, 0.5], tan_half_rot in [0, (float)tan(15 deg)]
+ * (rot in [0, 30] degrees), fovy in [0, 0.5), all finite, rows 8-byte and episode 4-byte aligned,
+ * no NULL pointer but active (RMBX_ERR_ARG otherwise, before the launch).
+ * ------------------------------------------------------------------------------------------- */
+#define RMBX_CAMERA_JITTER_PLANE 0x40000800
+#define RMBX_CAMERA_JITTER_MAX_CAMERAS 64
+
+typedef struct rmbx_camera_jitter_params {
+  float pos;          /* P, metres, [0, 0.5] */
+  float tan_half_rot; /* T = (float)tan(radians(R) / 2), R in [0, 30] degrees */
+  float fovy;         /* F, relative, [0, 0.5) */
+} rmbx_camera_jitter_params;
+
+int rmbx_camera_jitter_draw(uint64_t seed, const int32_t* episode, const rmbx_camera_jitter_params* p, int ncam,
+                            double* rows, const uint8_t* active, int n, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Policy vision-trunk epilogues (ResNet-18 with frozen BN folded into the convs), NHWC.

@@ -56,6 +56,7 @@ SIGNATURES = {
     "rmbx_engine_step_profiled": (_c_int, [_c_p, _c_int, _c_p, _c_p]),
     "rmbx_dynamics_draw": (_c_int, [ctypes.c_uint64, _c_p, _c_p, _c_p, _c_p, _c_int, _c_p]),
     "rmbx_engine_bind_dynamics": (_c_int, [_c_p, _c_p, _c_p]),
+    "rmbx_camera_jitter_draw": (_c_int, [ctypes.c_uint64, _c_p, _c_p, _c_int, _c_p, _c_p, _c_int, _c_p]),
     "rmbx_arm_ik": (_c_int, [_c_p] * 5 + [_c_int, _c_int, _c_p]),
     "rmbx_arm_fk": (_c_int, [_c_p] * 4 + [_c_int, _c_p]),
     "rmbx_motion_state": (_c_int, [_c_p] * 9 + [_c_int, _c_p, _c_int, _c_int, _c_p]),
@@ -150,7 +151,7 @@ class SceneTables(ctypes.Structure):
                 ("tflag", _c_p), ("geom_texid", _c_p), ("geom_matinfo", _c_p), ("tex_rgba", _c_p), ("tex_desc", _c_p),
                 ("tex_level_adr", _c_p), ("ntex", ctypes.c_int32), ("sky_rgb", ctypes.c_float * 6),
                 ("bvh_nodes", _c_p), ("bvh_tri", _c_p), ("bvh_root", _c_p), ("light_dir", ctypes.c_float * 3),
-                ("shadows", ctypes.c_int32), ("samp", _c_p), ("samples", ctypes.c_int32)]
+                ("shadows", ctypes.c_int32), ("samp", _c_p), ("samples", ctypes.c_int32), ("cam_rows", _c_p)]
 
 
 class RenderCache(ctypes.Structure):
@@ -286,6 +287,16 @@ class DynamicsParams(ctypes.Structure):
 
 
 DYNAMICS_PLANE = 0x40000700  # include/rmbx.h RMBX_DYNAMICS_PLANE
+
+
+class CameraJitterParams(ctypes.Structure):
+    """rmbx_camera_jitter_params (include/rmbx.h)."""
+
+    _fields_ = [("pos", ctypes.c_float), ("tan_half_rot", ctypes.c_float), ("fovy", ctypes.c_float)]
+
+
+CAMERA_JITTER_PLANE = 0x40000800  # include/rmbx.h RMBX_CAMERA_JITTER_PLANE
+CAMERA_JITTER_MAX_CAMERAS = 64  # include/rmbx.h RMBX_CAMERA_JITTER_MAX_CAMERAS
 
 assert ctypes.sizeof(PerturbParams) == 48
 # include/rmbx.h RMBX_PERTURB_PLANE_*

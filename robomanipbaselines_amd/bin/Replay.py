@@ -13,6 +13,10 @@ Rollout<Policy>_<Env>_world<idx>_<success|failure>_ep<episode>_step<k>.png.
 --as_seen (a run recorded with --perturb): the header's perturbation is applied to the re-rendered
 frame with the row's episode and rollout_time_idx, the keys the live run used, so the image of a step
 the policy read is the frame it read (the trace itself holds the clean scene).
+
+A run recorded with --camera_jitter: the header's spec and seed give every recorded episode's camera
+rows again (keyed by the episode, not by the slot it ran in); they are drawn and bound before
+rendering, so the frames stay the live step's.  --as_seen composes with it.
 """
 
 import argparse
@@ -87,10 +91,20 @@ def as_seen_of(header):
     return spec_from_dict(header["perturb"]), int(header["seed"]) & (2**64 - 1), list(header["camera_names"])
 
 
-def render_rows(renderer, rows, idx, cameras, device, batch_bytes=BATCH_BYTES, as_seen=None):
+def camera_jitter_of(header):
+    """The (spec, seed) of the recording run's --camera_jitter, or None for a trace recorded without it."""
+    from ..common.camera_jitter import spec_from_dict
+
+    if header.get("camera_jitter") is None:
+        return None
+    return spec_from_dict(header["camera_jitter"]), int(header["seed"]) & (2**64 - 1)
+
+
+def render_rows(renderer, rows, idx, cameras, device, batch_bytes=BATCH_BYTES, as_seen=None, camera_jitter=None):
     """u8 [len(idx), H, W * len(cameras), 3] host array: the rows `idx` of the episode drawn by every
     camera, the cameras side by side.  The steps are the renderer's batch, in batches that fit.
-    as_seen: as_seen_of(header), to perturb every frame as the policy of the recording run saw it."""
+    as_seen: as_seen_of(header), to perturb every frame as the policy of the recording run saw it.
+    camera_jitter: camera_jitter_of(header), to render every step with its episode's camera rows."""
     import torch
 
     from .. import kernels as K
@@ -108,6 +122,14 @@ def render_rows(renderer, rows, idx, cameras, device, batch_bytes=BATCH_BYTES, a
         dev = {k: torch.from_numpy(np.ascontiguousarray(rows[k][sel])).to(device) for k in ("gxpos", "gxmat", "xpos", "xquat")}
         eng = types.SimpleNamespace(n_env=t, ngeom=ngeom, nbody=nbody, **dev)
         rgb = torch.empty((t, H, W, 3), dtype=torch.uint8, device=device)
+        if camera_jitter is not None:
+            # the batch's steps are the renderer's envs: each gets the rows of its episode
+            spec, seed = camera_jitter
+            episode = torch.from_numpy(np.ascontiguousarray(rows["episode"][sel], dtype=np.int32)).to(device)
+            cam_rows = torch.empty((len(renderer.cam_names), t, 8), dtype=torch.float64, device=device)
+            P, T, F = spec.strengths()
+            K.camera_jitter_draw(seed, episode, cam_rows, pos=float(P), tan_half_rot=float(T), fovy=float(F))
+            renderer.bind_camera_rows(cam_rows)
         for c, cam in enumerate(cameras):
             renderer.render(eng, cam, rgb=rgb)
             if as_seen is not None and as_seen[0].touches_images:
@@ -119,6 +141,8 @@ def render_rows(renderer, rows, idx, cameras, device, batch_bytes=BATCH_BYTES, a
                                 contrast=spec.contrast, gain=spec.gain, noise=spec.noise, occ_h=occ_h, occ_w=occ_w,
                                 rgb_out=rgb)
             out[b0:b0 + t, :, c * W:(c + 1) * W] = rgb.cpu().numpy()
+    if camera_jitter is not None:
+        renderer.bind_camera_rows(None)
     return out
 
 
@@ -154,6 +178,7 @@ def main(argv=None):
     if unknown:
         raise ValueError(f"unknown camera(s) {unknown}; the scene has {header['camera_names']}")
     as_seen = as_seen_of(header) if args.as_seen else None
+    camera_jitter = camera_jitter_of(header)
     from ..common.image_io import write_png
 
     renderer = make_renderer(header, args.device, args.shadows, args.offsamples)
@@ -165,7 +190,7 @@ def main(argv=None):
     group = int(max(1, BATCH_BYTES // per_image))
     for g0 in range(0, len(idx), group):
         part = idx[g0:g0 + group]
-        images = render_rows(renderer, rows, part, cameras, args.device, as_seen=as_seen)
+        images = render_rows(renderer, rows, part, cameras, args.device, as_seen=as_seen, camera_jitter=camera_jitter)
         for i, image in zip(part, images):
             path = os.path.abspath(os.path.join(args.output_image_dir, image_name(header, record, rows["step"][i])))
             write_png(path, image)

@@ -38,6 +38,7 @@ from ..common.data_key import DataKey, action_key_codes, state_key_codes
 from ..common.data_utils import make_meta_info
 from ..common.episode_trace import TraceWriter, parse_episodes, row_bytes, select_mask
 from ..common import actuation as ACT
+from ..common import camera_jitter as CJ
 from ..common import dynamics as DYN
 from ..common.perturb import Perturber, parse_spec
 
@@ -70,6 +71,9 @@ class BatchedRolloutBase:
         # the parsed --dynamics spec (None: off); ValueError for a bad key or value
         self.dynamics_spec = (None if getattr(self.args, "dynamics", None) is None
                               else DYN.parse_spec(self.args.dynamics))
+        # the parsed --camera_jitter spec (None: off); ValueError for a bad key or value
+        self.camera_jitter_spec = (None if getattr(self.args, "camera_jitter", None) is None
+                                   else CJ.parse_spec(self.args.camera_jitter))
         torch.manual_seed(self.args.seed)
         np.random.seed(self.args.seed)
         self.device = torch.device(self.args.device)
@@ -90,6 +94,7 @@ class BatchedRolloutBase:
         self._perturb = None  # the common.perturb.Perturber of a run with --perturb
         self._actuation = None  # the common.actuation.Actuator of a run with --actuation
         self._dynamics = None  # the common.dynamics.Dynamics of a run with --dynamics
+        self._camera_jitter = None  # the common.camera_jitter.CameraJitter of a run with --camera_jitter
 
     def attach_phase_timer(self, timer):
         """Record HIP events at the policy / render / physics / glue boundaries of every env-step
@@ -197,6 +202,15 @@ class BatchedRolloutBase:
                                  "inertia, and the servo gains (kp, kv) are multiplied by a factor uniform in "
                                  "(1 - S, 1 + S). An episode meets the same world in any slot, shard or re-run; "
                                  "common.dynamics.scales(seed, episodes, spec) gives the factors on the host")
+        parser.add_argument("--camera_jitter", type=str, nargs="+", default=None, metavar="KEY=VALUE",
+                            help="jitter every camera's pose and field of view per episode, in the renderer (the "
+                                 "rule: include/rmbx.h, rmbx_camera_jitter_draw): pos=P (metres, [0, 0.5]: each "
+                                 "component of the mount's displacement uniform in +-P), rot=R (degrees, [0, 30]: a "
+                                 "rotation about the camera's own axes, below R per axis), fovy=F ([0, 0.5): fovy "
+                                 "times a factor uniform in (1 - F, 1 + F)). An episode sees the same cameras in any "
+                                 "slot, shard or re-run; common.camera_jitter.rows(seed, episodes, spec, ncam) gives "
+                                 "the rows on the host. The point cloud of DiffusionPolicy3d is still unprojected "
+                                 "with the nominal fovy: the policy believes the calibrated intrinsics")
         if self.require_task_desc:
             parser.add_argument("--task_desc", type=str, required=True)
         self.set_additional_args(parser)
@@ -219,6 +233,8 @@ class BatchedRolloutBase:
             ACT.parse_spec(self.args.actuation)  # ValueError for a bad key or value
         if self.args.dynamics is not None:
             DYN.parse_spec(self.args.dynamics)  # ValueError for a bad key or value
+        if self.args.camera_jitter is not None:
+            CJ.parse_spec(self.args.camera_jitter)  # ValueError for a bad key or value
         if self.args.num_episodes is not None:
             if self.args.num_episodes < 1:
                 raise ValueError("--num_episodes must be at least 1")
@@ -439,6 +455,18 @@ class BatchedRolloutBase:
         self._dynamics.draw(self._lockstep_rows)
         print(f"[{self.__class__.__name__}] Dynamics: {self.dynamics_spec}", flush=True)
 
+    # -- camera jitter (--camera_jitter) --------------------------------------------------------------
+    def _camera_jitter_begin(self):
+        """The CameraJitter of this run (made once: it binds its rows to the env's renderer), the draw
+        of the lockstep rows' episodes -- before env.reset renders the first observation -- and its one
+        printed line."""
+        if self._camera_jitter is None:
+            self._camera_jitter = CJ.CameraJitter(self.camera_jitter_spec, self.args.seed, self.env.renderer, self.n,
+                                                  self.device)
+        self._lockstep_rows_begin()
+        self._camera_jitter.draw(self._lockstep_rows)
+        print(f"[{self.__class__.__name__}] Camera jitter: {self.camera_jitter_spec}", flush=True)
+
     def action_stats(self):
         """The statistics denormalize_data turns the policy's output into the action with."""
         return self.model_meta_info["action"]
@@ -481,6 +509,8 @@ class BatchedRolloutBase:
         self.world_idx = self.env.modify_world(world_idx=world)
         if getattr(self, "dynamics_spec", None) is not None:
             self._dynamics_begin()
+        if getattr(self, "camera_jitter_spec", None) is not None:
+            self._camera_jitter_begin()
         self.obs, self.info = self.env.reset(seed=self.args.seed)
         self._bind_state_stats()
         dev = self.device
@@ -591,6 +621,8 @@ class BatchedRolloutBase:
             header["actuation"] = self.actuation_spec.as_dict()
         if getattr(self, "dynamics_spec", None) is not None:  # the world each recorded episode ran in
             header["dynamics"] = self.dynamics_spec.as_dict()
+        if getattr(self, "camera_jitter_spec", None) is not None:  # what Replay binds before it renders
+            header["camera_jitter"] = self.camera_jitter_spec.as_dict()
         self._trace = TraceWriter(directory, header, trace)
         # the size the run can reach: an episode ends by max_duration + the post-success second
         dt = env.frame_skip * env.sim_timestep
@@ -830,6 +862,8 @@ class BatchedRolloutBase:
             K.sched_active(self.sched, n_pre, out=self._step_mask)
             if getattr(self, "_dynamics", None) is not None:  # the new episodes' worlds, before their forward pass
                 self._dynamics.draw(st.slot_episode, active=st.recycled)
+            if getattr(self, "_camera_jitter", None) is not None:  # the new episodes' cameras, before their first render
+                self._camera_jitter.draw(st.slot_episode, active=st.recycled)
             self.env.refresh(active=st.recycled)
             self.obs, self.reward, self.info = self.env._get_obs(), self.env.reward, self.env._get_info()
             self._mark("glue")
@@ -920,6 +954,8 @@ class BatchedRolloutBase:
                 self.result["actuation"] = self.actuation_spec.as_dict()
             if getattr(self, "dynamics_spec", None) is not None:
                 self.result["dynamics"] = self.dynamics_spec.as_dict()
+            if getattr(self, "camera_jitter_spec", None) is not None:
+                self.result["camera_jitter"] = self.camera_jitter_spec.as_dict()
         if self.args.save_last_image:
             self.save_rgb_images(v)
         if rank == 0 and self.args.result_filename is not None:
@@ -978,6 +1014,8 @@ class BatchedRolloutBase:
                 self.result["actuation"] = self.actuation_spec.as_dict()
             if getattr(self, "dynamics_spec", None) is not None:
                 self.result["dynamics"] = self.dynamics_spec.as_dict()
+            if getattr(self, "camera_jitter_spec", None) is not None:
+                self.result["camera_jitter"] = self.camera_jitter_spec.as_dict()
             if self.args.result_filename is not None:
                 print(f"[{self.__class__.__name__}] Save the rollout results: {self.args.result_filename}")
                 with open(self.args.result_filename, "w") as f:

@@ -258,6 +258,9 @@ struct RenderArgs {
   const float4* bvh_nodes;
   const int32_t* bvh_tri;
   const int32_t* bvh_root;
+  // camera jitter (include/rmbx.h rmbx_camera_jitter_draw; null: every env renders with cam): the
+  // rows [n][8] = (d, q, s) of the camera being rendered
+  const double* cam_rows;
 };
 
 // 4 samples per pixel (include/rmbx.h rmbx_scene_tables, "Samples"): what the MS instantiations and
@@ -428,16 +431,44 @@ __device__ void sample_texture(const RenderArgs& a, int tex, int type, const flo
   for (int i = 0; i < 3; i++) c[i] = c0[i] + fr * (c1[i] - c0[i]);
 }
 
+// JIT: the instantiations launched when camera jitter rows are bound (a.cam_rows; the host picks them).
+// A compile-time parameter, not a branch on the pointer: the instantiations without it are then the code
+// they were before the rows existed (a block-uniform branch alone moved their register assignment and
+// cost 0.3 % of the render phase).
+// The field of view env `env` renders with: the camera's, scaled by the env's row (block-uniform: read
+// once per block, ahead of every pixel loop)
+template <bool JIT>
+__device__ __forceinline__ float camera_fovy(const RenderArgs& a, int env) {
+  if constexpr (JIT) return (float)((double)a.cam.fovy_deg * a.cam_rows[8 * (size_t)env + 7]);
+  else return a.cam.fovy_deg;
+}
+
 // camera pose of env `env` in world: R (columns = camera axes), p
+template <bool JIT>
 __device__ __forceinline__ void camera_frame(const RenderArgs& a, int env, CamFrame& cf) {
 #pragma clang fp contract(off)  // bit-identical in every kernel it is inlined into
   double Rb[9], Rc[9], R[9], t[3];
   const double* bq = a.xquat + ((size_t)env * a.nbody + a.cam.body) * 4;
   const double* bp = a.xpos + ((size_t)env * a.nbody + a.cam.body) * 3;
-  quat2mat(bq, Rb);
-  quat2mat(a.cam.quat, Rc);
-  matmul3(Rb, Rc, R);
-  matvec3(Rb, a.cam.pos, t);
+  if constexpr (!JIT) {
+    quat2mat(bq, Rb);
+    quat2mat(a.cam.quat, Rc);
+    matmul3(Rb, Rc, R);
+    matvec3(Rb, a.cam.pos, t);
+  } else {
+    // the env's jittered camera in its body's frame (include/rmbx.h: pos' = pos + d, quat' = quat (x) q,
+    // the sums in the header's order so that the host's composition is these bits)
+    const double* row = a.cam_rows + 8 * (size_t)env;
+    const double b0 = row[3], b1 = row[4], b2 = row[5], b3 = row[6];
+    const double a0 = a.cam.quat[0], a1 = a.cam.quat[1], a2 = a.cam.quat[2], a3 = a.cam.quat[3];
+    const double cp[3] = {a.cam.pos[0] + row[0], a.cam.pos[1] + row[1], a.cam.pos[2] + row[2]};
+    const double cq[4] = {a0 * b0 - a1 * b1 - a2 * b2 - a3 * b3, a0 * b1 + a1 * b0 + a2 * b3 - a3 * b2,
+                          a0 * b2 - a1 * b3 + a2 * b0 + a3 * b1, a0 * b3 + a1 * b2 - a2 * b1 + a3 * b0};
+    quat2mat(bq, Rb);
+    quat2mat(cq, Rc);
+    matmul3(Rb, Rc, R);
+    matvec3(Rb, cp, t);
+  }
   for (int i = 0; i < 9; i++) cf.R[i] = (float)R[i];
   for (int i = 0; i < 3; i++) cf.p[i] = (float)(bp[i] + t[i]);
 }
@@ -620,10 +651,11 @@ __device__ __forceinline__ void tri_cover(const RenderArgsOf<MS>& a, const TriCa
   tflag[(py / RENDER_TILE) * a.tiles_x + px / RENDER_TILE] = 1;  // (every writer stores the same 1)
 }
 
+template <bool JIT>
 __device__ __forceinline__ void mesh_frames_block(const RenderArgs& a, int env, CamFrame& cf, float (*mR)[9],
                                                   float (*mc)[3], int* mvis, float tanh_, float aspect) {
   const int tid = threadIdx.x;
-  if (tid == 0) camera_frame(a, env, cf);
+  if (tid == 0) camera_frame<JIT>(a, env, cf);
   __syncthreads();
   if (tid < a.nmesh) {
     mesh_frame(a, env, tid, cf, mR[tid], mc[tid]);
@@ -642,7 +674,7 @@ __device__ __forceinline__ void mesh_frames_block(const RenderArgs& a, int env, 
   __syncthreads();
 }
 
-template <bool MS>
+template <bool MS, bool JIT = false>
 __global__ void __launch_bounds__(RASTER_THREADS) raster_kernel(RenderArgsOf<MS> a, int chunks) {
   __shared__ CamFrame cf;
   __shared__ float mR[MAX_MESH][9], mc[MAX_MESH][3];
@@ -653,9 +685,9 @@ __global__ void __launch_bounds__(RASTER_THREADS) raster_kernel(RenderArgsOf<MS>
   const int chunk = lin / a.n_env, env = lin - chunk * a.n_env;
   if (chunk >= chunks) return;
   if (a.active && !a.active[env]) return;
-  const float tanh_ = tanf(0.5f * a.cam.fovy_deg * 3.14159265358979f / 180.0f);
+  const float tanh_ = tanf(0.5f * camera_fovy<JIT>(a, env) * 3.14159265358979f / 180.0f);
   const float aspect = (float)a.cam.width / (float)a.cam.height;
-  mesh_frames_block(a, env, cf, mR, mc, mvis, tanh_, aspect);
+  mesh_frames_block<JIT>(a, env, cf, mR, mc, mvis, tanh_, aspect);
   if (a.dbg & 16) return;  // (timing probe: the per-block frames only)
   // every lane stays to the end (the wave's pixel work is shared by all 64 lanes below)
   const int j = chunk * RASTER_THREADS + threadIdx.x;
@@ -904,7 +936,7 @@ __device__ __forceinline__ void store_policy(const RenderArgs& a, int env, int p
 #endif
 // MS: one sample pass of the 4-sample mode (CM 0 only): the rays go through the pass's sample position
 // instead of the pixel centre, and the only output is the 8-bit colour, summed into a.samp
-template <bool VIS, int CM, bool SH = false, bool MS = false>
+template <bool VIS, int CM, bool SH = false, bool MS = false, bool JIT = false>
 __global__ void __launch_bounds__(256, SH ? RMBX_RENDER_SH_MINW : RMBX_RENDER_MINW) render_kernel(RenderArgsOf<MS> a) {
   __shared__ PrimCam prims[MAX_PRIM];
   __shared__ int order[MAX_PRIM];        // the block's primitives sorted front to back, once
@@ -929,11 +961,11 @@ __global__ void __launch_bounds__(256, SH ? RMBX_RENDER_SH_MINW : RMBX_RENDER_MI
   constexpr int mode = CM;
   if (CM != 0 && (a.dirty[env] != 0) != (CM == 2)) return;
   const int W = a.cam.width, H = a.cam.height;
-  const float tanh_ = tanf(0.5f * a.cam.fovy_deg * 3.14159265358979f / 180.0f);
+  const float tanh_ = tanf(0.5f * camera_fovy<JIT>(a, env) * 3.14159265358979f / 180.0f);
   const float aspect = (float)W / (float)H;
   // cosine of the widest ray (image corner) against the view axis
   const float cos_max = rsqrtf(1.0f + tanh_ * tanh_ * (1.0f + aspect * aspect));
-  if (tid == 0) camera_frame(a, env, cf);
+  if (tid == 0) camera_frame<JIT>(a, env, cf);
   __syncthreads();
   if constexpr (VIS) {
     if (tid < a.nmesh) {
@@ -1421,17 +1453,19 @@ __global__ void __launch_bounds__(256) resolve_kernel(RenderArgsMS a) {
   if (a.policy) store_policy(a, env, px, py, W, H, hw, pix, u);
 }
 
-// Static-background cache validity, one wave per env: the camera body's pose and every static
-// primitive's pose are compared (exactly) with the snapshot the env's cache was built from; any
-// difference (or the NaN snapshot of a new cache) marks the env dirty -- its render pass rebuilds
-// the cache -- and takes the new snapshot.
+// Static-background cache validity, one wave per env: the camera body's pose, every static
+// primitive's pose and, when rows are bound, the env's camera jitter row are compared (exactly) with
+// the snapshot the env's cache was built from; any difference (or the NaN snapshot of a new cache)
+// marks the env dirty -- its render pass rebuilds the cache -- and takes the new snapshot.
 __global__ void __launch_bounds__(64) render_cache_check_kernel(RenderArgs a, const int32_t* static_prims,
                                                                int nstatic, double* snap, uint8_t* dirty) {
   const int env = blockIdx.x;
   if (a.active && !a.active[env]) return;
-  const int n = 7 + 12 * nstatic, body = a.cam.body;
+  // (with jitter rows bound the env's row is part of the snapshot, after the poses)
+  const int npose = 7 + 12 * nstatic, n = npose + (a.cam_rows ? 8 : 0), body = a.cam.body;
   double* sn = snap + (size_t)env * n;
   auto value = [&](int i) -> double {
+    if (i >= npose) return a.cam_rows[8 * (size_t)env + i - npose];
     if (i < 3) return a.xpos[((size_t)env * a.nbody + body) * 3 + i];
     if (i < 7) return a.xquat[((size_t)env * a.nbody + body) * 4 + i - 3];
     const int j = (i - 7) / 12, k = (i - 7) - 12 * j;
@@ -1520,6 +1554,8 @@ extern "C" int rmbx_render_scene_cached(const rmbx_camera* cam, const rmbx_scene
   a.bvh_nodes = reinterpret_cast<const float4*>(scene->bvh_nodes);
   a.bvh_tri = scene->bvh_tri;
   a.bvh_root = scene->bvh_root;
+  RMBX_CHECK_ARG(((uintptr_t)scene->cam_rows & 7) == 0, "cam_rows is not 8-byte aligned");
+  a.cam_rows = scene->cam_rows;
   // 4 samples per pixel: the colour outputs come from four sample passes and the resolve; depth and
   // hit_geom from the ordinary pixel-centre pass, which then writes no colour
   RMBX_CHECK_ARG(scene->samples == 0 || scene->samples == 1 || scene->samples == 4,
@@ -1581,6 +1617,23 @@ extern "C" int rmbx_render_scene_cached(const rmbx_camera* cam, const rmbx_scene
   const size_t nblocks = (size_t)n_env * a.groups;
   RMBX_CHECK_ARG(nblocks < (1ull << 31), "grid too large");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  // with camera jitter rows bound every kernel that reads the camera is its JIT instantiation
+  const bool jit = a.cam_rows != nullptr;
+#define RMBX_RENDER_ARGS(...) __VA_ARGS__
+#define RMBX_LAUNCH_RENDER(targs, args)                                                                                    \
+  do {                                                                                                                     \
+    if (jit)                                                                                                               \
+      hipLaunchKernelGGL((rmbx::render_kernel<RMBX_RENDER_ARGS targs, true>), dim3((unsigned)nblocks), dim3(256), 0, st, args); \
+    else                                                                                                                   \
+      hipLaunchKernelGGL((rmbx::render_kernel<RMBX_RENDER_ARGS targs, false>), dim3((unsigned)nblocks), dim3(256), 0, st, args); \
+  } while (0)
+#define RMBX_LAUNCH_RASTER(ms, args)                                                                                       \
+  do {                                                                                                                     \
+    if (jit)                                                                                                               \
+      hipLaunchKernelGGL((rmbx::raster_kernel<ms, true>), dim3((unsigned)rblocks), dim3(RASTER_THREADS), 0, st, args, chunks); \
+    else                                                                                                                   \
+      hipLaunchKernelGGL((rmbx::raster_kernel<ms, false>), dim3((unsigned)rblocks), dim3(RASTER_THREADS), 0, st, args, chunks); \
+  } while (0)
   const int chunks = (scene->ntri + RASTER_THREADS - 1) / RASTER_THREADS;
   const size_t rblocks = (size_t)chunks * n_env;
   RMBX_CHECK_ARG(!meshes || rblocks < (1ull << 31), "raster grid too large");
@@ -1598,16 +1651,16 @@ extern "C" int rmbx_render_scene_cached(const rmbx_camera* cam, const rmbx_scene
       m.soy = pattern[k][1];
       m.sfirst = k == 0;
       if (meshes) {
-        hipLaunchKernelGGL(rmbx::raster_kernel<true>, dim3((unsigned)rblocks), dim3(RASTER_THREADS), 0, st, m, chunks);
+        RMBX_LAUNCH_RASTER(true, m);
         RMBX_CHECK_LAUNCH();
         if (shadows)
-          hipLaunchKernelGGL((rmbx::render_kernel<true, 0, true, true>), dim3((unsigned)nblocks), dim3(256), 0, st, m);
+          RMBX_LAUNCH_RENDER((true, 0, true, true), m);
         else
-          hipLaunchKernelGGL((rmbx::render_kernel<true, 0, false, true>), dim3((unsigned)nblocks), dim3(256), 0, st, m);
+          RMBX_LAUNCH_RENDER((true, 0, false, true), m);
       } else if (shadows) {
-        hipLaunchKernelGGL((rmbx::render_kernel<false, 0, true, true>), dim3((unsigned)nblocks), dim3(256), 0, st, m);
+        RMBX_LAUNCH_RENDER((false, 0, true, true), m);
       } else {
-        hipLaunchKernelGGL((rmbx::render_kernel<false, 0, false, true>), dim3((unsigned)nblocks), dim3(256), 0, st, m);
+        RMBX_LAUNCH_RENDER((false, 0, false, true), m);
       }
       RMBX_CHECK_LAUNCH();
     }
@@ -1626,25 +1679,25 @@ extern "C" int rmbx_render_scene_cached(const rmbx_camera* cam, const rmbx_scene
   if (meshes) {
     // pass 1: the meshes' nearest triangle per pixel into the visibility buffer (empty on entry:
     // the ray-cast pass clears every key and tile flag it consumes)
-    hipLaunchKernelGGL(rmbx::raster_kernel<false>, dim3((unsigned)rblocks), dim3(RASTER_THREADS), 0, st, a, chunks);
+    RMBX_LAUNCH_RASTER(false, a);
     RMBX_CHECK_LAUNCH();
     if (use_cache) {
-      hipLaunchKernelGGL((rmbx::render_kernel<true, 1>), dim3((unsigned)nblocks), dim3(256), 0, st, a);
+      RMBX_LAUNCH_RENDER((true, 1, false, false), a);
       RMBX_CHECK_LAUNCH();
-      hipLaunchKernelGGL((rmbx::render_kernel<true, 2>), dim3((unsigned)nblocks), dim3(256), 0, st, a);
+      RMBX_LAUNCH_RENDER((true, 2, false, false), a);
     } else if (shade_shadows) {
-      hipLaunchKernelGGL((rmbx::render_kernel<true, 0, true>), dim3((unsigned)nblocks), dim3(256), 0, st, a);
+      RMBX_LAUNCH_RENDER((true, 0, true, false), a);
     } else {
-      hipLaunchKernelGGL((rmbx::render_kernel<true, 0>), dim3((unsigned)nblocks), dim3(256), 0, st, a);
+      RMBX_LAUNCH_RENDER((true, 0, false, false), a);
     }
   } else if (use_cache) {
-    hipLaunchKernelGGL((rmbx::render_kernel<false, 1>), dim3((unsigned)nblocks), dim3(256), 0, st, a);
+    RMBX_LAUNCH_RENDER((false, 1, false, false), a);
     RMBX_CHECK_LAUNCH();
-    hipLaunchKernelGGL((rmbx::render_kernel<false, 2>), dim3((unsigned)nblocks), dim3(256), 0, st, a);
+    RMBX_LAUNCH_RENDER((false, 2, false, false), a);
   } else if (shade_shadows) {
-    hipLaunchKernelGGL((rmbx::render_kernel<false, 0, true>), dim3((unsigned)nblocks), dim3(256), 0, st, a);
+    RMBX_LAUNCH_RENDER((false, 0, true, false), a);
   } else {
-    hipLaunchKernelGGL((rmbx::render_kernel<false, 0>), dim3((unsigned)nblocks), dim3(256), 0, st, a);
+    RMBX_LAUNCH_RENDER((false, 0, false, false), a);
   }
   RMBX_CHECK_LAUNCH();
   return RMBX_OK;

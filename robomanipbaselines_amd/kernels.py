@@ -912,6 +912,35 @@ def dynamics_draw(seed, episode, scale, friction=0.0, damping=0.0, mass=0.0, gai
 
 
 # ------------------------------------------------------------------------------------------
+# Per-episode jitter rows of the cameras (--camera_jitter)
+# ------------------------------------------------------------------------------------------
+def camera_jitter_draw(seed, episode, rows, pos=0.0, tan_half_rot=0.0, fovy=0.0, active=None):
+    """The jitter rows of include/rmbx.h (rmbx_camera_jitter_draw): rows f64 [ncam, n, 8] = (d, q, s)
+    per camera of the rows' episodes i32 [n], written in place; a row with active u8 [n] == 0 is not
+    written for any camera.  The strengths are the f32 values the kernel reads (tan_half_rot is
+    float32(tan(radians(rot) / 2))).  Shapes and dtypes are checked before the device.  Returns rows."""
+    seed = int(seed)
+    if not 0 <= seed < 2**64:
+        raise ValueError(f"seed must be an unsigned 64-bit value (got {seed})")
+    _chk(episode, torch.int32, name="episode")
+    if episode.dim() != 1 or episode.shape[0] < 1:
+        raise ValueError(f"episode must have shape [n], n >= 1 (got {tuple(episode.shape)})")
+    n = int(episode.shape[0])
+    _chk(rows, torch.float64, name="rows")
+    if rows.dim() != 3 or rows.shape[0] < 1 or tuple(rows.shape[1:]) != (n, 8):
+        raise ValueError(f"rows must have shape [ncam, {n}, 8], ncam >= 1 (got {tuple(rows.shape)})")
+    if active is not None:
+        _chk(active, torch.uint8, (n,), "active")
+    for t, name in ((rows, "rows"), (active, "active")):
+        if t is not None and t.device != episode.device:
+            raise ValueError(f"{name} is on {t.device}, episode on {episode.device}")
+    p = N.CameraJitterParams(float(pos), float(tan_half_rot), float(fovy))
+    N.call("rmbx_camera_jitter_draw", seed, N.ptr(episode), ctypes.byref(p), int(rows.shape[0]), N.ptr(rows),
+           N.ptr(active), n, N.stream_ptr())
+    return rows
+
+
+# ------------------------------------------------------------------------------------------
 # Point-cloud observation (3D diffusion policy)
 # ------------------------------------------------------------------------------------------
 def focal_scaling(fovy_deg, height):

@@ -258,6 +258,7 @@ class Renderer:
         self.prim_static = torch.tensor(stat, device=device) if self.nprim else None
         self.static_prims = torch.tensor(np.nonzero(stat)[0].astype(np.int32), device=device)
         self._caches = {}
+        self._cam_rows = None  # camera jitter rows f64 [ncam, n, 8] (bind_camera_rows), or None
         self.width, self.height = width, height
         self.cam_names = [str(x) for x in arrays["names_cam"]]
         self.znear = float(arrays["_znear"]) * float(arrays["_extent"])
@@ -280,6 +281,24 @@ class Renderer:
             c.std[k] = IMAGENET_STD[k]
         return c
 
+    def bind_camera_rows(self, rows):
+        """Bind the per-env camera jitter rows (include/rmbx.h rmbx_camera_jitter_draw): a device tensor
+        f64 [ncam, n, 8], ncam the scene's cameras in their order, read by every later render (env e of
+        camera c renders with rows[c, e]; the tensor is caller-owned and may be rewritten between
+        renders).  None unbinds: every env renders with the scene's cameras, bit for bit a Renderer that
+        never had rows bound.  The static-background caches are dropped either way (their snapshots
+        hold the rows)."""
+        if rows is not None:
+            if not isinstance(rows, torch.Tensor) or rows.dtype != torch.float64 or not rows.is_contiguous():
+                raise ValueError("camera rows must be a contiguous float64 tensor")
+            if rows.device.type != self.device.type or (self.device.index is not None
+                                                        and rows.device.index != self.device.index):
+                raise ValueError(f"camera rows are on {rows.device}, the renderer on {self.device}")
+            if rows.dim() != 3 or rows.shape[0] != len(self.cam_names) or rows.shape[1] < 1 or rows.shape[2] != 8:
+                raise ValueError(f"camera rows must have shape [{len(self.cam_names)}, n, 8] (got {tuple(rows.shape)})")
+        self._cam_rows = rows
+        self._caches = {}
+
     def _cache(self, camera_name, cam, n):
         """The static-background cache of a world-fixed camera (include/rmbx.h rmbx_render_cache), or
         None (a camera on a moving body, a scene without static primitives, a shadowed or 4-sample
@@ -295,7 +314,9 @@ class Renderer:
         ent = self._caches.get(camera_name)
         if ent is None or ent[0] != (n, H, W):
             buf = torch.empty(n * H * W * 2, dtype=torch.int32, device=self.device)
-            snap = torch.full((n * (7 + 12 * nst),), float("nan"), dtype=torch.float64, device=self.device)
+            # (with camera rows bound the snapshot holds the env's row after the poses)
+            nsnap = 7 + 12 * nst + (8 if self._cam_rows is not None else 0)
+            snap = torch.full((n * nsnap,), float("nan"), dtype=torch.float64, device=self.device)
             dirty = torch.zeros(n, dtype=torch.uint8, device=self.device)
             c = N.RenderCache()
             c.prim_static, c.static_prims, c.nstatic = self.prim_static.data_ptr(), self.static_prims.data_ptr(), nst
@@ -343,6 +364,12 @@ class Renderer:
                 self._samp = torch.empty(n * H * W, dtype=torch.int32, device=self.device)
             self._scene.samp = self._samp.data_ptr()
         cache = self._cache(camera_name, cam, n)
+        if self._cam_rows is not None:
+            if self._cam_rows.shape[1] != n:
+                raise ValueError(f"camera rows are bound for {self._cam_rows.shape[1]} envs, the engine has {n}")
+            self._scene.cam_rows = self._cam_rows[self.cam_names.index(camera_name)].data_ptr()
+        else:
+            self._scene.cam_rows = None
         try:
             N.call("rmbx_render_scene_cached", ctypes.byref(cam), ctypes.byref(self._scene),
                    N.ptr(engine.gxpos), N.ptr(engine.gxmat), N.ptr(engine.xpos), N.ptr(engine.xquat),
