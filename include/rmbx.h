@@ -1310,6 +1310,7 @@ int rmbx_action_perturb(const double* action, double* out, uint8_t* mask_out, do
  * 107-138: resize, ToDtype(scale), * 2 - 1) plus the obs encoder's eval centre crop.
  * rmbx_resize_f32: cv2.resize of f32 [n][H][W] depth to [n][rh][rw]
  * (RolloutDiffusionPolicy3d.py:138-145).
+ * n = 0 launches nothing (src and dst may then be NULL); sizes are checked all the same.
  * ------------------------------------------------------------------------------------------- */
 int rmbx_resize_crop_u8(const uint8_t* src, int n_env, int H, int W, int C, int rh, int rw, int y0,
                         int x0, int ch, int cw, float a, float b, void* dst, int dst_dtype,
@@ -1328,6 +1329,7 @@ int rmbx_resize_f32(const float* src, float* dst, int n_env, int H, int W, int r
  * min_bound / max_bound f64[3] host (NULL = no bound); norm_type 0 gaussian ((x - a) / b) or
  * 1 limits (b * (x - a) + c), a/b/c f64[6] host; out f32 [n][K][6] normalised (x, y, z, r, g, b),
  * raw f64 [n][K][6] optional (before normalisation), count i32 [n] = points after the crop.
+ * n = 0 launches nothing (depth, rgb, out, count may then be NULL); sizes are checked all the same.
  * ------------------------------------------------------------------------------------------- */
 int rmbx_pointcloud_fps(const float* depth, const uint8_t* rgb, int n_env, int H, int W,
                         double focal_scaling, const double* min_bound, const double* max_bound,
@@ -1364,6 +1366,9 @@ int rmbx_pointcloud_fps(const float* depth, const uint8_t* rgb, int n_env, int H
  *   active u8 [n_env]: 0 = h, c and pred of that env untouched; NULL = all active
  *   pred f32 [n_env][state_dim]
  * Supported: 1 <= hidden <= 128, 1 <= state_dim, state_dim + key_dim <= 256, key_dim >= 0.
+ *
+ * Both: n_env = 0 launches nothing (the per-env pointers, not the weights, may then be NULL); sizes are
+ * checked all the same.
  * ------------------------------------------------------------------------------------------- */
 int rmbx_sarnn_attention(const float* images, const float* w1, const float* b1, const float* w2,
                          const float* b2, const float* w3, const float* b3, float* keys, int n_env,

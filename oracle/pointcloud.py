@@ -39,7 +39,9 @@ def observation(depth, rgb, fovy, min_bound, max_bound, K, stats):
     """depth f32 [H, W], rgb u8 [H, W, 3] -> (normalised f32 [K, 6], raw f64 [K, 6], count)."""
     xyz, col = glue.depth_to_pointcloud(depth, fovy, rgb)
     pc = np.concatenate((xyz, col), axis=1)
-    pc = glue.crop_bb(pc, np.asarray(min_bound), np.asarray(max_bound))
+    # a missing bound is not applied (crop_pointcloud_bb's min_bound=None / max_bound=None)
+    pc = glue.crop_bb(pc, None if min_bound is None else np.asarray(min_bound),
+                      None if max_bound is None else np.asarray(max_bound))
     idx = fps_indices(pc, K)
     raw = pc[idx]
     t = stats["norm_config"]["type"] if "norm_config" in stats else "gaussian"

@@ -143,11 +143,13 @@ int grid_for(size_t n) {
 extern "C" int rmbx_resize_crop_u8(const uint8_t* src, int n_env, int H, int W, int C, int rh, int rw, int y0,
                                    int x0, int ch, int cw, float a, float b, void* dst, int dst_dtype,
                                    void* stream) {
-  RMBX_CHECK_ARG(src && dst, "rmbx_resize_crop_u8: null pointer");
+  RMBX_CHECK_ARG(n_env >= 0, "rmbx_resize_crop_u8: n_env = %d must be >= 0", n_env);
   RMBX_CHECK_ARG(H > 0 && W > 0 && C > 0 && C <= 4 && rh > 0 && rw > 0, "rmbx_resize_crop_u8: bad sizes");
   RMBX_CHECK_ARG(y0 >= 0 && x0 >= 0 && ch > 0 && cw > 0 && y0 + ch <= rh && x0 + cw <= rw,
                  "rmbx_resize_crop_u8: crop (%d,%d,%d,%d) outside %dx%d", y0, x0, ch, cw, rh, rw);
   RMBX_CHECK_ARG(dst_dtype >= 0 && dst_dtype <= 2, "rmbx_resize_crop_u8: dst_dtype must be 0, 1 or 2");
+  // an empty batch has no device memory behind it: its pointers may be NULL
+  RMBX_CHECK_ARG(n_env == 0 || (src && dst), "rmbx_resize_crop_u8: null pointer");
   if (n_env == 0) return RMBX_OK;
   rmbx::ImgArgs g{src, H, W, C, rh, rw, y0, x0, ch, cw, a, b, dst, dst_dtype, n_env};
   hipLaunchKernelGGL(rmbx::resize_crop_u8_kernel, dim3(rmbx::grid_for((size_t)n_env * ch * cw)), dim3(256), 0,
@@ -158,8 +160,9 @@ extern "C" int rmbx_resize_crop_u8(const uint8_t* src, int n_env, int H, int W, 
 
 extern "C" int rmbx_resize_f32(const float* src, float* dst, int n_env, int H, int W, int rh, int rw,
                                void* stream) {
-  RMBX_CHECK_ARG(src && dst, "rmbx_resize_f32: null pointer");
+  RMBX_CHECK_ARG(n_env >= 0, "rmbx_resize_f32: n_env = %d must be >= 0", n_env);
   RMBX_CHECK_ARG(H > 0 && W > 0 && rh > 0 && rw > 0, "rmbx_resize_f32: bad sizes");
+  RMBX_CHECK_ARG(n_env == 0 || (src && dst), "rmbx_resize_f32: null pointer");
   if (n_env == 0) return RMBX_OK;
   hipLaunchKernelGGL(rmbx::resize_f32_kernel, dim3(rmbx::grid_for((size_t)n_env * rh * rw)), dim3(256), 0,
                      (hipStream_t)stream, src, dst, n_env, H, W, rh, rw);

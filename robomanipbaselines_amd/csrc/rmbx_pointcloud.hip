@@ -250,10 +250,13 @@ extern "C" int rmbx_pointcloud_fps(const float* depth, const uint8_t* rgb, int n
                                    int K, int norm_type, const double* norm_a, const double* norm_b,
                                    const double* norm_c, float* out, double* raw, int32_t* count,
                                    void* stream) {
-  RMBX_CHECK_ARG(depth && rgb && out && count && norm_a && norm_b, "rmbx_pointcloud_fps: null pointer");
+  RMBX_CHECK_ARG(n_env >= 0, "rmbx_pointcloud_fps: n_env = %d must be >= 0", n_env);
   RMBX_CHECK_ARG(H > 0 && W > 0 && (long)H * W <= (long)rmbx::PC_THREADS * rmbx::PC_PPT,
                  "rmbx_pointcloud_fps: image %dx%d exceeds %d pixels", W, H, rmbx::PC_THREADS * rmbx::PC_PPT);
   RMBX_CHECK_ARG(K > 0, "rmbx_pointcloud_fps: K must be positive");
+  // an empty batch has no device memory behind it: its pointers may be NULL
+  RMBX_CHECK_ARG(n_env == 0 || (depth && rgb && out && count), "rmbx_pointcloud_fps: null pointer");
+  RMBX_CHECK_ARG(norm_a && norm_b, "rmbx_pointcloud_fps: null pointer");
   RMBX_CHECK_ARG(norm_type == 0 || (norm_type == 1 && norm_c), "rmbx_pointcloud_fps: bad normalisation");
   if (n_env == 0) return RMBX_OK;
   rmbx::PcArgs a{};

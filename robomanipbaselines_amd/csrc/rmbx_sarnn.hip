@@ -267,10 +267,11 @@ __global__ void __launch_bounds__(kLstmThreads)
 extern "C" int rmbx_sarnn_attention(const float* images, const float* w1, const float* b1, const float* w2,
                                     const float* b2, const float* w3, const float* b3, float* keys, int n_env,
                                     int ncam, int S, int K, float temperature, void* stream) {
-  RMBX_CHECK_ARG(images, "rmbx_sarnn_attention: images is NULL");
-  RMBX_CHECK_ARG(w1 && b1 && w2 && b2 && w3 && b3, "rmbx_sarnn_attention: a weight or bias pointer is NULL");
-  RMBX_CHECK_ARG(keys, "rmbx_sarnn_attention: keys is NULL");
   RMBX_CHECK_ARG(n_env >= 0, "rmbx_sarnn_attention: n_env = %d must be >= 0", n_env);
+  // an empty batch has no device memory behind it: its per-env pointers may be NULL
+  RMBX_CHECK_ARG(images || n_env == 0, "rmbx_sarnn_attention: images is NULL");
+  RMBX_CHECK_ARG(w1 && b1 && w2 && b2 && w3 && b3, "rmbx_sarnn_attention: a weight or bias pointer is NULL");
+  RMBX_CHECK_ARG(keys || n_env == 0, "rmbx_sarnn_attention: keys is NULL");
   RMBX_CHECK_ARG(ncam >= 1 && ncam <= 4, "rmbx_sarnn_attention: ncam = %d outside [1, 4]", ncam);
   RMBX_CHECK_ARG(S >= 8 && S <= 128, "rmbx_sarnn_attention: S = %d outside [8, 128]", S);
   RMBX_CHECK_ARG(K >= 1 && K <= rmbx::kAttMaxK, "rmbx_sarnn_attention: K = %d outside [1, %d]", K, rmbx::kAttMaxK);
@@ -301,17 +302,18 @@ extern "C" int rmbx_sarnn_lstm_step(const float* state, const float* keys, float
                                     const float* w_hh, const float* b_ih, const float* b_hh, const float* w_dec,
                                     const float* b_dec, const uint8_t* active, float* pred, int n_env, int state_dim,
                                     int key_dim, int hidden, void* stream) {
-  RMBX_CHECK_ARG(state, "rmbx_sarnn_lstm_step: state is NULL");
-  RMBX_CHECK_ARG(h && c, "rmbx_sarnn_lstm_step: h or c is NULL");
+  RMBX_CHECK_ARG(n_env >= 0, "rmbx_sarnn_lstm_step: n_env = %d must be >= 0", n_env);
+  // an empty batch has no device memory behind it: its per-env pointers may be NULL
+  RMBX_CHECK_ARG(state || n_env == 0, "rmbx_sarnn_lstm_step: state is NULL");
+  RMBX_CHECK_ARG((h && c) || n_env == 0, "rmbx_sarnn_lstm_step: h or c is NULL");
   RMBX_CHECK_ARG(w_ih && w_hh && b_ih && b_hh && w_dec && b_dec,
                  "rmbx_sarnn_lstm_step: a weight or bias pointer is NULL");
-  RMBX_CHECK_ARG(pred, "rmbx_sarnn_lstm_step: pred is NULL");
-  RMBX_CHECK_ARG(n_env >= 0, "rmbx_sarnn_lstm_step: n_env = %d must be >= 0", n_env);
+  RMBX_CHECK_ARG(pred || n_env == 0, "rmbx_sarnn_lstm_step: pred is NULL");
   RMBX_CHECK_ARG(hidden >= 1 && hidden <= rmbx::kLstmThreads, "rmbx_sarnn_lstm_step: hidden = %d outside [1, %d]",
                  hidden, rmbx::kLstmThreads);
   RMBX_CHECK_ARG(state_dim >= 1, "rmbx_sarnn_lstm_step: state_dim = %d must be >= 1", state_dim);
   RMBX_CHECK_ARG(key_dim >= 0, "rmbx_sarnn_lstm_step: key_dim = %d must be >= 0", key_dim);
-  RMBX_CHECK_ARG(keys || key_dim == 0, "rmbx_sarnn_lstm_step: keys is NULL");
+  RMBX_CHECK_ARG(keys || key_dim == 0 || n_env == 0, "rmbx_sarnn_lstm_step: keys is NULL");
   RMBX_CHECK_ARG(state_dim <= rmbx::kLstmMaxIn && key_dim <= rmbx::kLstmMaxIn - state_dim,
                  "rmbx_sarnn_lstm_step: state_dim + key_dim = %d exceeds %d", state_dim + key_dim, rmbx::kLstmMaxIn);
   if (n_env == 0) return RMBX_OK;
